@@ -18,18 +18,26 @@ whole graph and MiniBatchKMeans is ~260 latency-bound sequential steps, so ``--m
 (default) runs N independent distillations, one graph per GPU (seed + rank), with no collective in
 the data path ("scaling": "weak"). ``--mode one-graph`` distils ONE graph over all ranks as the north
 star partitions it (gdd.sharded: labels pass by rows, cluster means by clusters, RCCL all-gathers,
-bit-identical to one GPU; "scaling": "strong"); at N > 1 the replicas line also carries that mode's
-time for the same graph under ``one_graph``.
+bit-identical to one GPU; "scaling": "strong"); at N > 1 the replicas line of a ``--full`` run also
+carries that mode's time for the same graph under ``one_graph``.
 
-The same line carries sub-records measured in this run: ``recsys`` (config 4's kmeans_cluster pair),
-``products`` (config 5 at full shape; at N = 1 also fp32 vs bf16 labels pass), ``reddit`` (config
-3's whole inductive path: GraphSAINT split, three role graphs, fit, means), and at N = 1 ``e2e``
-(the drop-in agent with main_transduct.sh's arxiv flags: stage times and the five GCN accuracies)
-and the CPU baselines. At N > 1 the recsys/products/reddit records distil ONE instance over all
-ranks as north_star splits it.
+A plain run sets up, warms up, times the K steps and prints the headline line (``value``,
+``ms_per_step`` and the workload's description); ``--dump-outputs DIR`` also writes what the last
+timed step returned (the distilled features and labels, the fit's labels and centres) as
+``DIR/<name>.npy``. The inputs depend on the arguments alone, so two builds can be compared output
+for output.
+
+With ``--full`` the same line also carries what takes runs of its own: the synchronised per-phase
+times, the hop's roofline and the labels pass's MFMA use, at N > 1 the ``one_graph`` time, and the
+sub-records ``recsys`` (config 4's kmeans_cluster pair), ``products`` (config 5 at full shape; at
+N = 1 also fp32 vs bf16 labels pass), ``reddit`` (config 3's whole inductive path: GraphSAINT
+split, three role graphs, fit, means), and at N = 1 ``e2e`` (the drop-in agent with
+main_transduct.sh's arxiv flags: stage times and the five GCN accuracies) and the CPU baselines. At
+N > 1 the recsys/products/reddit records distil ONE instance over all ranks as north_star splits
+it.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config arxiv] [--mode replicas|one-graph]
-                       [--no-cpu-baseline] [--no-extra] [--no-e2e]
+                       [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra] [--no-e2e]]
 """
 from __future__ import annotations
 
@@ -55,11 +63,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="arxiv")
     ap.add_argument("--mode", choices=("replicas", "one-graph"), default="replicas")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the phases, rooflines, sub-records, e2e run and CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the recsys / products / reddit / e2e sub-records (quick A/B runs)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the drop-in agent run")
-    return ap.parse_args()
+                    help="with --full: skip the recsys / products / reddit / e2e sub-records (quick A/B runs)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the drop-in agent run")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def setup_dist(n_gpus):
@@ -135,6 +150,9 @@ def main():
         labels_syn = gdd.argmax_rows(km.cluster_centers_device_)
         return feat_syn, labels_syn, km
 
+    # a Lloyd config's KMeans() draws from numpy's global generator, as the reference's call does:
+    # seeded here, so that the same arguments give the same outputs (the arxiv fit has its own seed)
+    np.random.seed(seed)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -143,13 +161,90 @@ def main():
     t0 = time.perf_counter()
     n_steps_km = []
     for _ in range(args.steps):
-        _, _, km = step(record=True)
+        feat_syn, labels_syn, km = step(record=True)
         n_steps_km.append(getattr(km, "n_steps_", getattr(km, "n_iter_", 0)))
     torch.cuda.synchronize()
     barrier(world)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     t_max = max_over_ranks(elapsed, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, feat_syn, labels_syn, km)
+    del feat_syn, labels_syn, km
+    hops = cfg.T - 1
+    out = {
+        "metric": "distill wallclock (SpMM+k-means) & test-acc parity, ogbn-arxiv r=0.5% @1-8 GPU",
+        "value": cfg.n * args.steps * (1 if one_graph else world) / t_max,
+        "unit": "nodes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * t_max / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if one_graph else "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic (Chung-Lu power-law graph + N(0,1) features of the ogbn-arxiv shape; "
+                "random linear logits)",
+        "config": {"workload": f"{cfg.name} pretrained_clustering hot path: normalize + "
+                               f"{hops} SpMM hops + MiniBatchKMeans(k={cfg.k}, b={cfg.batch}) + "
+                               "cluster means",
+                   "nodes": cfg.n, "nnz_in": nnz_in, "nnz_norm": prop_ev[-1][2], "feat_dim": cfg.d,
+                   "k": cfg.k,
+                   "parallelism": ("single GPU" if world == 1 else
+                                   (f"one graph over {world} ranks: labels pass by rows, cluster "
+                                    "means by clusters (RCCL all-gathers); normalise, propagation "
+                                    "and minibatch steps replicated") if one_graph else
+                                   f"replicas x{world}: one graph per GPU, no data-path collective"),
+                   "kmeans_steps": n_steps_km},
+        # what `value` counts at this world size (ADVICE r3): replicas are N independent graphs
+        # (aggregate throughput; ms_per_step stays one graph's distill wallclock); one-graph mode is
+        # the strong-scaling distillation of a single graph over all ranks
+        "value_basis": ("one graph on one GPU" if world == 1 else
+                        f"one graph distilled over {world} ranks (strong scaling)" if one_graph else
+                        f"{world} independent graphs, one per GPU (aggregate nodes/s over all ranks; "
+                        "ms_per_step is one graph's wallclock; the strong-scaling time of rank 0's "
+                        "graph over all ranks is under one_graph in a --full run)"),
+        "full": args.full,
+    }
+    if args.full:
+        def set_inputs(g, x):
+            nonlocal graph, X
+            graph, X = g, x
+        out.update(full_records(args, cfg, rank, world, dev, group, step, set_inputs, graph, X,
+                                A, X_h, W, b, prop_ev))
+    if rank == 0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, feat_syn, labels_syn, km, limit=64 << 20):
+    """What the last timed step handed its caller, one DIR/<name>.npy each: the distilled features
+    (k x d) and labels (k), the fit's node labels (N) and centres (k x C); fp32 as computed, integer
+    labels as fp64. An array over its share of `limit` bytes is cut to a fixed seeded sample of its
+    rows (none is at the shapes of gdd.synth.CONFIGS)."""
+    arrays = {"feat_syn": feat_syn, "labels_syn": labels_syn, "labels": km.labels_device_,
+              "cluster_centers": km.cluster_centers_device_}
+    os.makedirs(path, exist_ok=True)
+    share = limit // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            rows = np.random.default_rng(0).choice(a.shape[0], share // (a.nbytes // a.shape[0]),
+                                                   replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def full_records(args, cfg, rank, world, dev, group, step, set_inputs, graph, X, A, X_h, W, b, prop_ev):
+    """--full: the rest of the line, each part measured in runs of its own after the timed steps.
+    `step` is main()'s timed step, `set_inputs(graph, X)` rebinds the inputs it reads."""
+    import gdd
+    from gdd import synth
+    one_graph = args.mode == "one-graph"
     one_graph_rec = None
     if world > 1 and not one_graph:
         # the same graph (rank 0's) distilled over all ranks, for the strong-scaling comparison
@@ -158,6 +253,7 @@ def main():
             A1 = synth.chung_lu(cfg.n, cfg.avg_degree, cfg.seed)
             graph_1, X_1 = gdd.to_csr(A1, device=dev), torch.from_numpy(synth.features(cfg.n, cfg.d, cfg.seed)).to(dev)
             graph, X = graph_1, X_1
+            set_inputs(graph, X)
         g_all = dist.group.WORLD
         for _ in range(args.warmup):
             step(group=g_all)
@@ -176,6 +272,7 @@ def main():
                          "parallelism": f"one graph over {world} ranks (gdd.sharded)"}
         if rank != 0:
             graph, X = gdd.to_csr(A, device=dev), torch.from_numpy(X_h).to(dev)
+            set_inputs(graph, X)
 
     # per-phase wall times of one more (untimed) step, synchronised between phases (SURVEY §8(d):
     # hot-path wallclock by stage and nodes clustered per second = N / k-means wallclock)
@@ -249,39 +346,7 @@ def main():
     reddit = reddit_record(dev, with_cpu=with_cpu, group=g_all, world=world) if extra else None
     e2e = e2e_record(dev) if extra and world == 1 and not args.no_e2e else None
 
-    out = {
-        "metric": "distill wallclock (SpMM+k-means) & test-acc parity, ogbn-arxiv r=0.5% @1-8 GPU",
-        "value": cfg.n * args.steps * (1 if one_graph else world) / t_max,
-        "unit": "nodes/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * t_max / args.steps,
-        "higher_is_better": True,
-        "scaling": "strong" if one_graph else "weak",
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "data": "synthetic (Chung-Lu power-law graph + N(0,1) features of the ogbn-arxiv shape; "
-                "random linear logits)",
-        "config": {"workload": f"{cfg.name} pretrained_clustering hot path: normalize + "
-                               f"{hops} SpMM hops + MiniBatchKMeans(k={cfg.k}, b={cfg.batch}) + "
-                               "cluster means",
-                   "nodes": cfg.n, "nnz_in": nnz_in, "nnz_norm": nnz, "feat_dim": d,
-                   "k": cfg.k,
-                   "parallelism": ("single GPU" if world == 1 else
-                                   (f"one graph over {world} ranks: labels pass by rows, cluster "
-                                    "means by clusters (RCCL all-gathers); normalise, propagation "
-                                    "and minibatch steps replicated") if one_graph else
-                                   f"replicas x{world}: one graph per GPU, no data-path collective"),
-                   "kmeans_steps": n_steps_km},
-        # what `value` counts at this world size (ADVICE r3): replicas are N independent graphs
-        # (aggregate throughput; ms_per_step stays one graph's distill wallclock); one-graph mode is
-        # the strong-scaling distillation of a single graph over all ranks
-        "value_basis": ("one graph on one GPU" if world == 1 else
-                        f"one graph distilled over {world} ranks (strong scaling)" if one_graph else
-                        f"{world} independent graphs, one per GPU (aggregate nodes/s over all ranks; "
-                        "ms_per_step is one graph's wallclock; the strong-scaling time of rank 0's "
-                        "graph over all ranks is under one_graph)"),
+    rec = {
         "phases_ms": phases,
         "nodes_clustered_per_s": cfg.n / (phases["kmeans"] * 1e-3) if phases.get("kmeans") else None,
         "roofline": {"bound": "hbm", "kernel": "k_hop (+ k_fixup): one propagation hop",
@@ -302,14 +367,10 @@ def main():
                                        "synthetic arxiv-shaped dataset") if e2e else None},
     }
     if one_graph_rec is not None:
-        out["one_graph"] = one_graph_rec
+        rec["one_graph"] = one_graph_rec
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(cfg, A, X_h)
-    if rank == 0:
-        print(json.dumps(out))
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        rec["cpu_baseline"] = cpu_baseline(cfg, A, X_h)
+    return rec
 
 
 def recsys_record(dev, with_cpu, reps=10, group=None, world=1):

@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 for r in $(seq 1 "$R"); do
   for L in "$A" "$B"; do
     echo "lib $L"
-    GDD_LIB_PATH=$L timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra --steps 20 --warmup 3 > "$OUT/run.log" 2>&1 || { tail -20 "$OUT/run.log"; exit 1; }
+    GDD_LIB_PATH=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra --steps 20 --warmup 3 > "$OUT/run.log" 2>&1 || { tail -20 "$OUT/run.log"; exit 1; }
     python3 -c "
 import json,sys
 d=[json.loads(l) for l in open('$OUT/run.log') if l.startswith('{')][-1]

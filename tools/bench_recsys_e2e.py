@@ -90,7 +90,9 @@ def alidisplay(epochs=500):
     """The drop-in driver on the reference's real dataset beside the reference's own trajectory."""
     import contextlib
     import io
-    z = np.load(os.path.join(ROOT, "tests", "golden", "golden_alidisplay.npz"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from golden_util import load
+    z = load("golden_alidisplay.npz")
     ref = open(os.path.join(ROOT, "tests", "golden", "golden_alidisplay_full_stdout.txt")).read().splitlines()
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "Ali-Display"))

@@ -61,7 +61,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/ClustGDD"
 OUT = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, os.path.join(ROOT, "graph-distillation-for-recommendation_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from gdd import synth  # noqa: E402  (input generators only)
+from golden_util import save_parts  # noqa: E402  (fixtures over the committed-file size limit)
 
 
 class _Stub(types.ModuleType):
@@ -172,7 +174,7 @@ def g3_kmeans(recsys):
     E = synth.blobs(2000, 64, 100, seed=33)
     lab, cen = recsys.kmeans_cluster(E, n_clusters=200, seed=42, minibatch=False)
     out.update({"rs_X": E, "rs_labels": lab.astype(np.int64), "rs_centers": cen.astype(np.float32)})
-    np.savez_compressed(os.path.join(OUT, "golden_kmeans.npz"), **out)
+    save_parts("golden_kmeans.npz", out)
 
 
 def sha(a):
@@ -818,7 +820,7 @@ def g6r_alidisplay(recsys):
         recsys.compute_svd_embeddings = orig_svd
     assert all(np.array_equal(embs[0][j], e[j]) for e in embs for j in range(2)), "svds not repeatable"
     out["user_emb"], out["item_emb"] = embs[0]
-    np.savez_compressed(os.path.join(OUT, "golden_alidisplay.npz"), **out)
+    save_parts("golden_alidisplay.npz", out)
     for tag, text in stdout.items():
         with open(os.path.join(OUT, f"golden_alidisplay_{tag}_stdout.txt"), "w") as f:
             f.write(text)
