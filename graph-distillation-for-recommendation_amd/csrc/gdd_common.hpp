@@ -109,6 +109,7 @@ bool bf16q_norms_fit(int dim, int k);
 //   fold_no_pad       the Lloyd M-step gathers X itself instead of its zero-padded copy
 //   estep_no_pad      the bounded E-step's row lists read X instead of the padded copy
 //   fold_slice=F      M-step clusters above F x the mean size fold in slices (default 1.5; 0: off)
+//   reduce_tile=N     the fixed-point M-step's bucketed rows per block (a power of two, 64 .. 16384)
 //   group_split       the multi-launch label grouping where the one-launch form fits
 //   center_seq        KMeans' centring by the sequential column chains
 //   bf16_v1           the r03 bf16 labels pass (gdd_kmeans.hip) instead of the r06 one (gdd_bf16.hip)

@@ -1720,3 +1720,322 @@ extern "C" int gdd_lloyd_update(int64_t n, int dim, int k, const float* parts, i
   GDD_LAUNCHED();
   return GDD_OK;
 }
+
+// ---- the order-free fixed-point M-step (gdd.sharded.ShardedKMeans(mstep="reduce")) -----------------
+// int64 sums of q = rint(x * 2^e_f) are exact and associative: no member order has to be kept, so a
+// rank sums its own rows, one SUM all-reduce of k*dim + k + 1 words follows, and the result is the
+// same bits for any number of ranks, any row split and any reduction order (include/gdd.h states
+// the arithmetic). The rank's rows are bucketed by label (group_dev, whose order is not needed here,
+// only its buckets), then tiles of the bucketed order are summed: a tile lies inside one cluster
+// unless it crosses a boundary, so a thread keeps one int64 register per (cluster run, column), the
+// workers of a block meet in LDS for the tile's first cluster, and the block leaves with one 8-byte
+// integer atomic per column for it; runs of further clusters in the tile leave with one atomic per
+// (worker, run, column). Atomics per launch <= (tiles + workers' boundary crossings) * dim.
+namespace gdd {
+namespace {
+constexpr int kRedTileMax = 1024;   // bucketed rows per block: the largest of 1024, 512, 256 that
+constexpr int kRedTileMin = 256;    // still gives kRedMinBlocks blocks (GDD_FORCE=reduce_tile=N pins it)
+constexpr int kRedMinBlocks = 4096;
+constexpr int kRedUnroll = 8;   // row loads in flight per thread
+
+// frexp exponent of a positive fp32 from its bits (subnormals: bit_length(mantissa) - 149)
+__device__ __forceinline__ int frexp_exp_bits(uint32_t b) {
+  const int be = (int)(b >> 23);
+  return be ? be - 126 : (32 - __clz((int)b)) - 149;
+}
+
+// amax[f] = max_i bits(|X[i,f]|): non-negative floats order as their bit patterns
+__global__ __launch_bounds__(256) void k_col_absmax(int64_t n, int dim, const float* __restrict__ X,
+                                                    uint32_t* __restrict__ amax) {
+  __shared__ uint32_t s[512];
+  for (int f = threadIdx.x; f < dim; f += 256) s[f] = 0u;
+  __syncthreads();
+  const int64_t total = n * dim;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int f = (int)(e % dim);
+  const int fstep = (int)(stride % dim);
+  for (; e < total; e += stride) {
+    const uint32_t b = __float_as_uint(X[e]) & 0x7fffffffu;
+    if (b > s[f]) atomicMax(&s[f], b);
+    f += fstep;
+    if (f >= dim) f -= dim;
+  }
+  __syncthreads();
+  for (int g = threadIdx.x; g < dim; g += 256)
+    if (s[g]) atomicMax(&amax[g], s[g]);
+}
+
+// in place: the column's abs-max bits -> e_f = 62 - L - E_f (0 for an all-zero column)
+__global__ void k_reduce_exponents(int dim, int L, int32_t* __restrict__ exps) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= dim) return;
+  const uint32_t b = (uint32_t)exps[f];
+  exps[f] = b ? 62 - L - frexp_exp_bits(b) : 0;
+}
+
+// 2^e as a double, -1022 <= e <= 1023 (e_f lies in [62 - 63 - 128, 62 + 148])
+__device__ __forceinline__ double pow2_f64(int e) {
+  return __longlong_as_double((long long)(e + 1023) << 52);
+}
+
+// rint(ldexp((double)x, e)): the product by 2^e is exact (no fp64 under- or overflow in e_f's range)
+__device__ __forceinline__ long long quantise(float x, double scale) {
+  return __double2ll_rn((double)x * scale);
+}
+
+// the cluster whose bucket holds position p < offsets[k]: the smallest j in [1, k] with offsets[j] > p, less 1
+__device__ __forceinline__ int bucket_of(const int32_t* __restrict__ offsets, int k, int64_t p) {
+  int lo = 1, hi = k;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)offsets[mid] > p) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo - 1;
+}
+
+// Grid (tiles of `tile` positions of the bucketed order, 64-column slices), 256 threads as 256 / G
+// workers of G lanes (G = 64, or the power of two >= dim for dim <= 32; tile is a multiple of 256 / G):
+// worker w sums positions [p0 + w*per, ..) of the tile, lane f_in its column.
+__global__ __launch_bounds__(256) void k_reduce_sum(int dim, const float* __restrict__ X,
+                                                    const int32_t* __restrict__ perm,
+                                                    const int32_t* __restrict__ offsets, int k,
+                                                    const int32_t* __restrict__ exps, int G, int tile,
+                                                    long long* __restrict__ buf, const int32_t* stop,
+                                                    int step_i) {
+  if (stopped(stop, step_i)) return;
+  __shared__ long long lacc[256];
+  const int64_t tot = offsets[k];
+  const int64_t p0 = (int64_t)blockIdx.x * tile;
+  if (p0 >= tot) return;  // uniform over the block
+  const int64_t pend = min(p0 + (int64_t)tile, tot);
+  const int tid = threadIdx.x, wk = tid / G, fi = tid - wk * G, nwk = 256 / G;
+  const int f = blockIdx.y * 64 + fi;
+  const bool act = f < dim;
+  const int per = tile / nwk;
+  const int64_t a = p0 + (int64_t)wk * per, b = min(a + (int64_t)per, pend);
+  const int cb0 = bucket_of(offsets, k, p0);
+  const double scale = act ? pow2_f64(exps[f]) : 0.0;
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(buf);
+  long long first = 0;  // this thread's part of the tile's first cluster
+  if (a < b) {
+    int cur = bucket_of(offsets, k, a);
+    int64_t end = offsets[cur + 1];
+    long long acc = 0;
+    int32_t rows[kRedUnroll], nxt[kRedUnroll];
+#pragma unroll
+    for (int u = 0; u < kRedUnroll; ++u) nxt[u] = a + u < b ? perm[a + u] : -1;
+    for (int64_t p = a; p < b; p += kRedUnroll) {
+      float xs[kRedUnroll];
+#pragma unroll
+      for (int u = 0; u < kRedUnroll; ++u) {  // the next batch's row ids fly with this batch's rows
+        rows[u] = nxt[u];
+        nxt[u] = p + kRedUnroll + u < b ? perm[p + kRedUnroll + u] : -1;
+      }
+#pragma unroll
+      for (int u = 0; u < kRedUnroll; ++u)
+        xs[u] = (act && rows[u] >= 0) ? X[(int64_t)rows[u] * dim + f] : 0.f;
+#pragma unroll
+      for (int u = 0; u < kRedUnroll; ++u) {
+        if (p + u >= b) break;
+        while (p + u >= end) {  // the run of `cur` ends (p + u < offsets[k], so cur + 1 <= k)
+          if (cur == cb0) first += acc;
+          else if (act && acc) atomicAdd(out + (int64_t)cur * dim + f, (unsigned long long)acc);
+          acc = 0;
+          ++cur;
+          end = offsets[cur + 1];
+        }
+        acc += quantise(xs[u], scale);
+      }
+    }
+    if (cur == cb0) first += acc;
+    else if (act && acc) atomicAdd(out + (int64_t)cur * dim + f, (unsigned long long)acc);
+  }
+  lacc[tid] = first;
+  __syncthreads();
+  if (tid < G && act) {
+    long long sum = 0;
+    for (int w = 0; w < nwk; ++w) sum += lacc[w * G + tid];
+    if (sum) atomicAdd(out + (int64_t)cb0 * dim + f, (unsigned long long)sum);
+  }
+}
+
+// the member counts (from the buckets) behind the sums
+__global__ void k_reduce_counts(int k, const int32_t* __restrict__ offsets, long long* __restrict__ counts,
+                                const int32_t* stop, int step_i) {
+  if (stopped(stop, step_i)) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < k) counts[c] = (long long)(offsets[c + 1] - offsets[c]);
+}
+
+// *word += #{i < m : labels[i] != old[i]}, old[i] = labels[i] there
+__global__ __launch_bounds__(256) void k_reduce_changed(int64_t m, const int32_t* __restrict__ labels,
+                                                        int32_t* __restrict__ old, long long* word,
+                                                        const int32_t* stop, int step_i) {
+  if (stopped(stop, step_i)) return;
+  __shared__ int s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  int cnt = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t v = labels[i];
+    if (v != old[i]) {
+      ++cnt;
+      old[i] = v;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_cnt)
+    atomicAdd(reinterpret_cast<unsigned long long*>(word), (unsigned long long)s_cnt);
+}
+
+// the update's front end: the reduced int64 sums -> fp32 sums (one rounding, then an exact scaling)
+// and the exact counts -> fp32 weights
+__global__ void k_reduce_front(int k, int dim, const long long* __restrict__ buf,
+                               const int32_t* __restrict__ exps, float* __restrict__ C_new,
+                               float* __restrict__ wsum, const int32_t* stop, int step_i) {
+  if (stopped(stop, step_i)) return;
+  const int64_t total = (int64_t)k * dim;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * blockDim.x) {
+    const int f = (int)(e % dim);
+    C_new[e] = ldexpf(__ll2float_rn(buf[e]), -exps[f]);
+    if (e < k) wsum[e] = __ll2float_rn(buf[total + e]);
+  }
+}
+
+// one block, after k_reduce_front (a stop set here must not cut that kernel's blocks short): the
+// labels-changed flag, and the empty-cluster stop at this very step, so the averaging and the
+// convergence test behind it do not run
+__global__ __launch_bounds__(256) void k_reduce_check(int k, const long long* __restrict__ counts,
+                                                      const long long* __restrict__ changed,
+                                                      LloydState* st, int it, int step_i) {
+  if (stopped(&st->stop_at, step_i)) return;
+  __shared__ int s_any;
+  if (threadIdx.x == 0) s_any = 0;
+  __syncthreads();
+  int any = 0;
+  for (int j = threadIdx.x; j < k; j += blockDim.x) any |= counts[j] == 0;
+  if (any) s_any = 1;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (*changed != 0) st->changed = 1;
+  if (s_any) {
+    st->reason = 3;
+    st->iter = it;
+    __hip_atomic_store(&st->stop_at, step_i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// group_dev's workspace for any row count up to n (a rank groups its own rows; the tile plan, and
+// with it the histogram matrix, is not monotone in the row count)
+size_t reduce_group_ws(int64_t n, int k) {
+  const int64_t cells = (int64_t)k * ((n + kTileUnit - 1) / kTileUnit);
+  const size_t bound = 2 * align256(sizeof(int32_t) * (size_t)cells) + align256(scan_i32_ws_bytes(cells)) + 256;
+  return std::max(group_ws(n, k), bound);
+}
+}  // namespace
+}  // namespace gdd
+
+extern "C" size_t gdd_lloyd_reduce_words(int dim, int k) {
+  return (size_t)std::max(k, 0) * (size_t)std::max(dim, 0) + (size_t)std::max(k, 0) + 1;
+}
+
+extern "C" size_t gdd_lloyd_reduce_ws_bytes(int64_t n, int dim, int k) {
+  n = std::max<int64_t>(n, 1);
+  k = std::max(k, 1);
+  return align256(sizeof(int32_t) * (size_t)n) + align256(sizeof(int32_t) * (size_t)(k + 1)) +
+         reduce_group_ws(n, k) + 1024;
+}
+
+extern "C" int gdd_lloyd_reduce_exponents(int64_t n, int dim, const float* X, int32_t* exps,
+                                          gdd_stream_t stream) {
+  GDD_REQUIRE(n > 0 && dim > 0 && dim <= 512 && X && exps, "lloyd_reduce_exponents: bad arguments");
+  hipStream_t s = to_hip(stream);
+  GDD_HIP(hipMemsetAsync(exps, 0, sizeof(int32_t) * (size_t)dim, s));
+  const unsigned grid = (unsigned)std::min<int64_t>((n * dim + 2047) / 2048, 2048);
+  k_col_absmax<<<grid, 256, 0, s>>>(n, dim, X, reinterpret_cast<uint32_t*>(exps));
+  GDD_LAUNCHED();
+  int L = 0;
+  while (L < 63 && (int64_t(1) << L) < n) ++L;  // bit_length(n - 1): n <= 2^L
+  k_reduce_exponents<<<blocks_of(dim), 256, 0, s>>>(dim, L, exps);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+extern "C" int gdd_lloyd_reduce_local(int64_t n, int64_t r0, int64_t r1, int dim, const float* X,
+                                      const int32_t* labels, int32_t* labels_old, int k,
+                                      const int32_t* exps, int64_t* buf, void* state, int it, void* ws,
+                                      size_t ws_bytes, gdd_stream_t stream) {
+  GDD_REQUIRE(n > 0 && n <= INT_MAX && 0 <= r0 && r0 <= r1 && r1 <= n && dim > 0 && dim <= 512 && k > 0 &&
+                  X && labels && labels_old && exps && buf && state && ws && it >= 0,
+              "lloyd_reduce_local: bad arguments");
+  hipStream_t s = to_hip(stream);
+  if (ws_bytes < gdd_lloyd_reduce_ws_bytes(n, dim, k))
+    return fail(GDD_E_WORKSPACE, "lloyd_reduce_local: workspace too small");
+  Carver cv(ws, ws_bytes);
+  int32_t* perm = cv.take<int32_t>(n);
+  int32_t* offsets = cv.take<int32_t>(k + 1);
+  const size_t gb = reduce_group_ws(n, k);
+  void* gws = cv.take<char>(gb);
+  if (!cv.ok()) return fail(GDD_E_WORKSPACE, "lloyd_reduce_local: workspace too small");
+  LloydState* st = static_cast<LloydState*>(state);
+  const int sa = 2 * it;
+  long long* b64 = reinterpret_cast<long long*>(buf);
+  // not gated: past a stop the caller's all-reduce still runs, on zeros
+  GDD_HIP(hipMemsetAsync(buf, 0, sizeof(int64_t) * gdd_lloyd_reduce_words(dim, k), s));
+  const int64_t m = r1 - r0;
+  if (m == 0) return GDD_OK;
+  int rc = group_dev(m, labels + r0, k, perm, offsets, gws, gb, &st->stop_at, sa, s);
+  if (rc) return rc;
+  k_reduce_counts<<<blocks_of(k), 256, 0, s>>>(k, offsets, b64 + (int64_t)k * dim, &st->stop_at, sa);
+  GDD_LAUNCHED();
+  int G = 64;
+  if (dim <= 32) {
+    G = 4;
+    while (G < dim) G <<= 1;
+  }
+  int tile = kRedTileMax;
+  while (tile > kRedTileMin && (m + tile - 1) / tile < kRedMinBlocks) tile >>= 1;
+  const int ft = (int)forced_value("reduce_tile", 0.0);
+  if (ft >= 64 && ft <= 16384 && (ft & (ft - 1)) == 0) tile = ft;  // a power of two >= 256 / G workers
+  const dim3 grid(blocks_of(m, tile), (unsigned)((dim + 63) / 64));
+  k_reduce_sum<<<grid, 256, 0, s>>>(dim, X + r0 * dim, perm, offsets, k, exps, G, tile, b64, &st->stop_at, sa);
+  GDD_LAUNCHED();
+  const unsigned cgrid = std::min<unsigned>(blocks_of(m), 2048);
+  k_reduce_changed<<<cgrid, 256, 0, s>>>(m, labels + r0, labels_old + r0, b64 + (int64_t)k * dim + k,
+                                         &st->stop_at, sa);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+extern "C" int gdd_lloyd_reduce_update(int dim, int k, const int64_t* buf, const int32_t* exps,
+                                       int from_cnew, float* C_new, float* wsum, const float* C_old,
+                                       float* shift, double tol, void* state, int it,
+                                       gdd_stream_t stream) {
+  GDD_REQUIRE(dim > 0 && dim <= 512 && k > 0 && (from_cnew || (buf && exps)) && C_new && wsum && C_old &&
+                  shift && state && it >= 0,
+              "lloyd_reduce_update: bad arguments");
+  hipStream_t s = to_hip(stream);
+  LloydState* st = static_cast<LloydState*>(state);
+  const int sb = 2 * it + 1;
+  if (!from_cnew) {
+    const long long* b64 = reinterpret_cast<const long long*>(buf);
+    const int64_t total = (int64_t)k * dim;
+    k_reduce_front<<<(unsigned)std::min<int64_t>((total + 255) / 256, 2048), 256, 0, s>>>(
+        k, dim, b64, exps, C_new, wsum, &st->stop_at, sb);
+    GDD_LAUNCHED();
+    k_reduce_check<<<1, 256, 0, s>>>(k, b64 + total, b64 + total + k, st, it, sb);
+    GDD_LAUNCHED();
+  }
+  k_avg_centers<<<k, 64, 0, s>>>(k, dim, C_new, wsum, C_old, shift, &st->stop_at, sb);
+  GDD_LAUNCHED();
+  k_lloyd_converge<<<1, 256, 0, s>>>(k, shift, tol, st, it, sb);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}

@@ -11,7 +11,10 @@ the reference file:line each entry point replaces):
 * :mod:`gdd.condense` — ``graph_sparse`` / ``graph_compress`` / ``ER_estimator`` /
   ``attaw_ER_estimator`` (ClustGDD's sparsification and cluster-level graph)
 * :class:`gdd.sharded.ShardedKMeans` — Lloyd on several ranks: the E-step partitioned by rows, the
-  M-step by clusters, all-gathers of the labels and the cluster slices (bit-identical to one GPU)
+  M-step by clusters, all-gathers of the labels and the cluster slices (bit-identical to one GPU);
+  ``mstep="reduce"`` (opt-in) sums each rank's rows as int64 fixed point and all-reduces the
+  k x (dim + 1) + 1 words once per iteration instead (bit-identical across world sizes and row
+  splits; its own arithmetic, not scikit-learn's ordered sums)
 * :mod:`gdd.agent` / :mod:`gdd.agent_induct` — the transductive and inductive ClustGDD agents;
   :mod:`gdd.train_clustgdd_transduct` / :mod:`gdd.train_clustgdd_induct` /
   :mod:`gdd.distill_recsys` — the drop-in command lines

@@ -92,6 +92,13 @@ SIGNATURES = {
                                  _c_int, _vp, _c_size, _vp]),
     "gdd_lloyd_update": (_c_int, [_c_i64, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                   ctypes.c_double, _vp, _c_int, _vp]),
+    "gdd_lloyd_reduce_words": (_c_size, [_c_int, _c_int]),
+    "gdd_lloyd_reduce_ws_bytes": (_c_size, [_c_i64, _c_int, _c_int]),
+    "gdd_lloyd_reduce_exponents": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp]),
+    "gdd_lloyd_reduce_local": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _c_int, _vp,
+                                        _vp, _vp, _c_int, _vp, _c_size, _vp]),
+    "gdd_lloyd_reduce_update": (_c_int, [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp,
+                                         ctypes.c_double, _vp, _c_int, _vp]),
     "gdd_skl_sqdist": (_c_int, [_c_int, _vp, _c_i64, _c_int, _vp, _vp, _vp]),
     "gdd_kmeans_plusplus_ws_bytes": (_c_size, [_c_i64, _c_int, _c_int]),
     "gdd_kmeans_plusplus_ws_bytes_k": (_c_size, [_c_i64, _c_int, _c_int, _c_int]),

@@ -26,10 +26,15 @@ from .graph import CSRGraph, induced_subgraph, normalize_adj, propagate, to_csr
 from .kmeans import KMeans, MiniBatchKMeans
 
 
-def _lloyd(n_clusters, group, **kw):
+def _lloyd(n_clusters, group, mstep="ordered", **kw):
     """KMeans on one GPU, or gdd.sharded.ShardedKMeans (rows/clusters partitioned, bit-identical)
-    when `group` spans several ranks."""
+    when `group` spans several ranks. ``mstep="reduce"`` (the order-free fixed-point M-step with one
+    all-reduce per iteration) goes to ShardedKMeans on any number of ranks, one included."""
     from .sharded import ShardedKMeans, world_of
+    if mstep == "reduce":
+        return ShardedKMeans(n_clusters=n_clusters, group=group, mstep="reduce", **kw)
+    if mstep != "ordered":
+        raise ValueError(f"mstep must be 'ordered' or 'reduce', got {mstep!r}")
     if group is not None and world_of(group)[1] > 1:
         return ShardedKMeans(n_clusters=n_clusters, group=group, **kw)
     return KMeans(n_clusters=n_clusters, **kw)

@@ -12,7 +12,11 @@ k-means work that scales with n is partitioned:
   [r·q, (r+1)·q) (q = ceil(k / R)) over ALL their members in sample order — the single-GPU order —
   and ONE all-gather of the k-row slices follows.
 
-Each value is therefore computed by the same kernel on the same operands as on one GPU:
+* opt-in, ``ShardedKMeans(mstep="reduce")``: the M-step by rows too — int64 fixed-point sums of the
+  rank's rows and ONE all-reduce of k*(dim+1)+1 words per iteration instead of the labels all-gather
+  (order-free, so bit-identical for any world size and row split; its own arithmetic).
+
+In the default mode each value is computed by the same kernel on the same operands as on one GPU:
 labels, centres, inertia, iteration counts and cluster means are bit-identical for every world
 size, and equal scikit-learn's (fixtures G3/G9) — the reference's call sites
 ``clustgdd_agent_transduct.py:102-125``, ``clustgdd_agent_induct.py:131-152`` and
@@ -111,6 +115,22 @@ def all_gather_slots(buf: torch.Tensor, m: int, group=None) -> None:
     parts = [torch.empty_like(host) for _ in range(world)]
     dist.all_gather(parts, host, group=group)
     buf.copy_(torch.cat(parts, 0).to(buf.device))
+
+
+def all_reduce_sum(buf: torch.Tensor, group=None) -> None:
+    """In place: every rank's `buf` ends with the element-wise sum over the ranks. RCCL for device
+    tensors (stream-ordered, no host sync); gloo stages through the host. For integer tensors the
+    result does not depend on the collective's algorithm (integer adds are associative)."""
+    rank, world = world_of(group)
+    if world == 1:
+        return
+    if buf.is_cuda and dist.get_backend(group) == "nccl":
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+        return
+    host = buf.cpu() if buf.is_cuda else buf
+    dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+    if host is not buf:
+        buf.copy_(host)
 
 
 def global_rank(group, r: int) -> int:
@@ -397,6 +417,32 @@ class DeviceOps:
                                              ctx.labels.data_ptr(), ctx.labels_old.data_ptr(), float(tol),
                                              ctx.state.data_ptr(), it, self.stream))
 
+    # -- the order-free fixed-point M-step (gdd_lloyd_reduce_*; mstep="reduce") ---------------------
+    def lloyd_reduce_begin(self, ctx):
+        """The int64 exchange buffer (k*dim sums, k counts, the changed count), the columns'
+        exponents and the local phase's workspace."""
+        dev = self.device
+        ctx.rbuf = torch.zeros(self.lib.gdd_lloyd_reduce_words(ctx.dim, ctx.k), dtype=torch.int64, device=dev)
+        ctx.exps = torch.zeros(ctx.dim, dtype=torch.int32, device=dev)
+        ctx.rws = _lib.workspace(self.lib.gdd_lloyd_reduce_ws_bytes(ctx.n, ctx.dim, ctx.k), dev)
+
+    def lloyd_reduce_exponents(self, ctx, X):
+        _lib.check(self.lib.gdd_lloyd_reduce_exponents(ctx.n, ctx.dim, X.data_ptr(), ctx.exps.data_ptr(),
+                                                       self.stream))
+
+    def lloyd_reduce_local(self, ctx, X, r0, r1, it):
+        _lib.check(self.lib.gdd_lloyd_reduce_local(ctx.n, r0, r1, ctx.dim, X.data_ptr(),
+                                                   ctx.labels.data_ptr(), ctx.labels_old.data_ptr(), ctx.k,
+                                                   ctx.exps.data_ptr(), ctx.rbuf.data_ptr(),
+                                                   ctx.state.data_ptr(), it, ctx.rws.data_ptr(),
+                                                   ctx.rws.numel(), self.stream))
+
+    def lloyd_reduce_update(self, ctx, from_cnew, C_new, C_old, tol, it):
+        _lib.check(self.lib.gdd_lloyd_reduce_update(ctx.dim, ctx.k, ctx.rbuf.data_ptr(), ctx.exps.data_ptr(),
+                                                    int(from_cnew), C_new.data_ptr(), ctx.wsum.data_ptr(),
+                                                    C_old.data_ptr(), ctx.shift.data_ptr(), float(tol),
+                                                    ctx.state.data_ptr(), it, self.stream))
+
     def lloyd_state_begin(self, ctx):
         """Start the state's device-to-host copy (pinned, stream-ordered); lloyd_state_end waits."""
         h = torch.empty(8, dtype=torch.int32, pin_memory=True)
@@ -571,10 +617,24 @@ class ShardedKMeans:
     says a row split pays, the device loop runs in phases — the E-step on this rank's rows, an
     all-gather of the labels, the replicated M-step (or, with ``split_columns``, this rank's feature
     columns and an all-gather of the column slices) and update; otherwise every rank runs the
-    single-GPU device loop (`gdd.KMeans`) on the replicated input, with no collective at all."""
+    single-GPU device loop (`gdd.KMeans`) on the replicated input, with no collective at all.
+
+    ``mstep="reduce"`` (opt-in, ``mode_ == "reduce"`` for every world size) splits the M-step too:
+    each rank sums its own rows as int64 fixed point (``q = rint(x * 2^e_f)``, the exponents fixed
+    once per fit so that no sum can overflow; include/gdd.h), ONE SUM all-reduce of
+    ``k*(dim+1)+1`` int64 words per iteration replaces the labels all-gather, and the sums are rounded
+    to fp32 once before the usual averaging and convergence test. Integer sums are exact and
+    associative, so the fit is bit-identical for any number of ranks, any row split and any
+    reduction order — but it is its own arithmetic, not scikit-learn's ordered fp32 chains: labels
+    and ``n_iter_`` agree with scikit-learn on the tested inputs, centres to a few 1e-6 relative."""
 
     def __init__(self, n_clusters=8, *, n_init="auto", max_iter=300, tol=1e-4, random_state=None,
-                 group=None, ops=None, device="cuda", split_columns=False):
+                 group=None, ops=None, device="cuda", split_columns=False, mstep="ordered"):
+        if mstep not in ("ordered", "reduce"):
+            raise ValueError(f"mstep must be 'ordered' or 'reduce', got {mstep!r}")
+        if mstep == "reduce" and split_columns:
+            raise ValueError("split_columns splits the ordered M-step; mstep='reduce' has no column split")
+        self.mstep = mstep
         self.n_clusters = n_clusters
         self.n_init = n_init
         self.max_iter = max_iter
@@ -591,7 +651,10 @@ class ShardedKMeans:
         group = self.group
         rank, world = world_of(group)
         n_all, dim_all = X.shape
-        if self.ops is None and not lloyd_rows_pay(n_all, dim_all, self.n_clusters, world):
+        reduce = self.mstep == "reduce"
+        if reduce and self.split_columns:
+            raise ValueError("split_columns splits the ordered M-step; mstep='reduce' has no column split")
+        if not reduce and self.ops is None and not lloyd_rows_pay(n_all, dim_all, self.n_clusters, world):
             # replicated: the single-GPU device loop on every rank (same RandomState, same bits)
             km = KMeans(n_clusters=self.n_clusters, n_init=self.n_init, max_iter=self.max_iter,
                         tol=self.tol, random_state=self.random_state, device=self.device).fit(X)
@@ -600,7 +663,7 @@ class ShardedKMeans:
                 setattr(self, a, getattr(km, a))
             self.mode_ = "replicated"
             return self
-        self.mode_ = "rows"
+        self.mode_ = "reduce" if reduce else "rows"
         ops = self.ops or DeviceOps(self.device)
         X = ops.tensor(X, dtype=torch.float32)
         n, dim = X.shape
@@ -617,6 +680,9 @@ class ShardedKMeans:
         tol_ = 0 if self.tol == 0 else np.mean(var) * self.tol
         n_init = 1 if self.n_init == "auto" else int(self.n_init)
         ctx = ops.lloyd_begin(n, dim, k, world, m, fw if split else 1)
+        if reduce:
+            ops.lloyd_reduce_begin(ctx)
+            ops.lloyd_reduce_exponents(ctx, Xc)  # on the device: no host sync
         labels = ctx.labels[:n]
         mine = ctx.parts[rank * k * fw:(rank + 1) * k * fw].view(k, fw) if split else None
         best = None
@@ -626,11 +692,17 @@ class ShardedKMeans:
             it0, resume, first_e = 0, False, 0
             while True:  # _kmeans_single_lloyd (:690-735), enqueued in chunks of iterations
                 ops.lloyd_clear(ctx, resume)
-                stop_at, reason, it_r, done = self._run_chunks(ops, ctx, Xc, Cb, it0, resume, first_e,
-                                                              (r0, r1, m), (f0, f1, fw, split), mine,
-                                                              tol_, group)
+                if reduce:
+                    stop_at, reason, it_r, done = self._run_chunks_reduce(ops, ctx, Xc, Cb, it0, resume,
+                                                                         first_e, (r0, r1, m), tol_, group)
+                else:
+                    stop_at, reason, it_r, done = self._run_chunks(ops, ctx, Xc, Cb, it0, resume, first_e,
+                                                                  (r0, r1, m), (f0, f1, fw, split), mine,
+                                                                  tol_, group)
                 if reason != 3:
                     break
+                if reduce:  # the rare path's one labels all-gather: the relocation reads every row's label
+                    all_gather_slots(ctx.labels, m, group)
                 # an empty cluster at iteration it_r (rare): the sums to C[(it+1) % 2], sklearn's
                 # relocation on the host (replicated, identical on every rank), then resume there
                 it = it_r
@@ -646,6 +718,8 @@ class ShardedKMeans:
                 lab, _ = ops.assign(Xc, C, r0, r1)
                 lab_full = all_gather_parts(lab, m, n, group)
             else:
+                if reduce:  # each rank holds its own rows' labels: the one all-gather of this init
+                    all_gather_slots(ctx.labels, m, group)
                 lab_full = labels.clone()
             sq = all_gather_parts(ops.point_sqdist(Xc, lab_full, C, r0, r1), m, n, group)
             inertia = ops.inertia(sq)
@@ -685,6 +759,36 @@ class ShardedKMeans:
                         ops.lloyd_update(ctx, None, ctx.dim, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
                 else:  # resume after a relocation: C[(i+1) % 2] already holds the relocated sums
                     ops.lloyd_update(ctx, None, fw, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
+                i += 1
+            handle = ops.lloyd_state_begin(ctx)
+            if pending is not None:
+                st = ops.lloyd_state_end(pending)  # the previous chunk's decision, read while this one runs
+                if st[0]:
+                    return st
+            pending = handle
+            ch = min(ch * 2, 8)
+        st = ops.lloyd_state_end(pending) if pending is not None else (0, 0, 0, 0)
+        if st[0]:
+            return st
+        return 0, 0, 0, self.max_iter  # ran out of iterations (sklearn's loop end)
+
+    def _run_chunks_reduce(self, ops, ctx, Xc, Cb, it0, resume, first_e, rows, tol_, group):
+        """:meth:`_run_chunks` for ``mstep="reduce"``: each iteration is the E-step on this rank's rows,
+        the rank's int64 sums / counts / changed count, ONE SUM all-reduce of that buffer, and the
+        replicated update from it. The collective is not gated by the stop word: past a stop the local
+        phase only zeroes the buffer, the all-reduce sums zeros, and nothing reads it — what a resume
+        after a relocation needs is in C[(i+1) % 2], wsum and the state word."""
+        r0, r1, m = rows
+        i, ch, pending = it0, 2, None
+        while i < self.max_iter:
+            for _ in range(min(ch, self.max_iter - i)):
+                if not (resume and i == it0):
+                    ops.lloyd_estep(ctx, Xc, Cb[i % 2], r0, r1, i == first_e, i)
+                    ops.lloyd_reduce_local(ctx, Xc, r0, r1, i)
+                    all_reduce_sum(ctx.rbuf, group)
+                    ops.lloyd_reduce_update(ctx, False, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
+                else:  # resume after a relocation: C[(i+1) % 2] already holds the relocated sums
+                    ops.lloyd_reduce_update(ctx, True, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
                 i += 1
             handle = ops.lloyd_state_begin(ctx)
             if pending is not None:

@@ -308,6 +308,39 @@ int gdd_lloyd_update(int64_t n, int dim, int k, const float* parts, int fw, floa
                      const float* wsum, const float* C_old, float* shift, const int32_t* labels,
                      int32_t* labels_old, double tol, void* state, int it, gdd_stream_t stream);
 
+/* The order-free M-step of the same phase loop (gdd.sharded.ShardedKMeans(mstep="reduce")): int64   */
+/* fixed-point partial sums, exact and associative, so the result is bit-identical for any number of */
+/* ranks, any row split and any reduction order; it does NOT keep scikit-learn's ordered fp32 chain. */
+/* Exponents (gdd_lloyd_reduce_exponents, once per fit, on the centred input Xc of n_total rows):     */
+/*   L = bit_length(n_total - 1); E_f = frexp exponent of max_i |Xc[i,f]|; exps[f] = 62 - L - E_f,    */
+/*   or 0 for an all-zero column. Then |sum q| <= 2^62 for any labelling: nothing can overflow.       */
+/* Quantise: q[i,f] = rint(ldexp((double)Xc[i,f], exps[f])) as int64, round-half-even.                */
+/* Buffer (int64, gdd_lloyd_reduce_words(dim, k) = k*dim + k + 1 words): [0, k*dim) the row-major     */
+/*   k x dim sums of q, [k*dim, k*dim + k) the member counts, then 1 word: the rows whose label       */
+/*   differs from labels_old.                                                                         */
+/* gdd_lloyd_reduce_local (step 2*it): zeroes buf (always, also past a stop), then for this rank's    */
+/*   rows [r0, r1) (r0 == r1 allowed) writes its sums, counts and changed count into buf and sets     */
+/*   labels_old[i] = labels[i] on those rows. labels/labels_old are the full n-row arrays.            */
+/*   ws: gdd_lloyd_reduce_ws_bytes(n, dim, k). The caller then SUM-all-reduces buf over the ranks.    */
+/* gdd_lloyd_reduce_update (step 2*it + 1), on the reduced buf: C_new[c,f] = ldexpf((float)S[c,f],    */
+/*   -exps[f]) (one round-to-nearest int64 -> fp32 conversion, then an exact scaling), wsum[c] =      */
+/*   (float)count[c] (a conversion of the exact integer count: unlike the ordered M-step's fp32       */
+/*   count, it does not stick at 2^24), the labels-changed flag = (changed word != 0); a cluster with */
+/*   count 0 stops the loop there with reason 3 (C_new holds the sums, wsum the counts, the flag      */
+/*   stays in the state). Otherwise _average_centers, _center_shift and the convergence test exactly  */
+/*   as gdd_lloyd_update. from_cnew != 0 (the resume after a relocation): buf is not read, C_new      */
+/*   already holds the relocated sums.                                                                */
+size_t gdd_lloyd_reduce_words(int dim, int k);
+size_t gdd_lloyd_reduce_ws_bytes(int64_t n, int dim, int k);
+int gdd_lloyd_reduce_exponents(int64_t n, int dim, const float* X, int32_t* exps, gdd_stream_t stream);
+int gdd_lloyd_reduce_local(int64_t n, int64_t r0, int64_t r1, int dim, const float* X,
+                           const int32_t* labels, int32_t* labels_old, int k, const int32_t* exps,
+                           int64_t* buf, void* state, int it, void* ws, size_t ws_bytes,
+                           gdd_stream_t stream);
+int gdd_lloyd_reduce_update(int dim, int k, const int64_t* buf, const int32_t* exps, int from_cnew,
+                            float* C_new, float* wsum, const float* C_old, float* shift, double tol,
+                            void* state, int it, gdd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------- */
 /* Greedy k-means++ seeding, sklearn _kmeans_plusplus (sklearn/cluster/_kmeans.py:174-272) on the    */
 /* device. Host supplies the reference RNG draws: first_id (random_state.choice) and                 */
