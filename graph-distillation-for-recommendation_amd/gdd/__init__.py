@@ -15,6 +15,9 @@ the reference file:line each entry point replaces):
   ``mstep="reduce"`` (opt-in) sums each rank's rows as int64 fixed point and all-reduces the
   k x (dim + 1) + 1 words once per iteration instead (bit-identical across world sizes and row
   splits; its own arithmetic, not scikit-learn's ordered sums)
+* :func:`gdd.svd.truncated_svd`, :func:`gdd.svd.svd_embeddings` — the recommender's clustering
+  embeddings as a deterministic fp64 block subspace iteration on the device (opt-in:
+  ``distill_recsys --svd_backend device``)
 * :mod:`gdd.agent` / :mod:`gdd.agent_induct` — the transductive and inductive ClustGDD agents;
   :mod:`gdd.train_clustgdd_transduct` / :mod:`gdd.train_clustgdd_induct` /
   :mod:`gdd.distill_recsys` — the drop-in command lines
@@ -27,9 +30,11 @@ from .graph import (CSRGraph, induced_subgraph, normalize_adj, normalize_adj_ten
                     to_csr)
 from .kmeans import KMeans, MiniBatchKMeans
 from .sharded import ShardedKMeans, shard_rows
+from .svd import svd_embeddings, truncated_svd
 
 __all__ = [
     "CSRGraph", "to_csr", "normalize_adj", "normalize_adj_tensor", "propagate", "spmm",
     "KMeans", "MiniBatchKMeans", "ShardedKMeans", "shard_rows", "cluster_mean", "argmax_rows",
     "induced_subgraph", "group_by_label", "graph_sparse", "graph_compress", "ER_estimator", "attaw_ER_estimator",
+    "truncated_svd", "svd_embeddings",
 ]

@@ -142,6 +142,21 @@ SIGNATURES = {
     "gdd_select_csr_ws_bytes": (_c_size, [_c_i64]),
     "gdd_select_csr": (_c_int, [_c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_size,
                                 _vp]),
+    "gdd_svd_max_block": (_c_int, []),
+    "gdd_spmm_f64": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_int, _vp, _vp, _vp]),
+    "gdd_gram_f64_ws_bytes": (_c_size, [_c_i64, _c_int]),
+    "gdd_gram_f64": (_c_int, [_c_i64, _c_int, _vp, _vp, _c_int, _vp, _c_size, _vp]),
+    "gdd_tsmm_f64": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp]),
+    "gdd_chol_inv_f64": (_c_int, [_c_int, _vp, _vp, _vp, _vp]),
+    "gdd_cholqr2_ws_bytes": (_c_size, [_c_i64, _c_int]),
+    "gdd_cholqr2_f64": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_svd_segment_ws_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
+    "gdd_svd_segment": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp,
+                                 _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_svd_residuals_ws_bytes": (_c_size, [_c_i64, _c_int]),
+    "gdd_svd_residuals": (_c_int, [_c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_svd_finalize": (_c_int, [_c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp]),
 }
 
 _lib = None

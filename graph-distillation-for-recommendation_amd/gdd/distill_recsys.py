@@ -9,7 +9,8 @@ Stage by stage (reference line ranges):
 1. data (:45-117): the Rankformer text files; the interaction matrix is a host scipy CSR;
 2. embeddings (:124-155): ``scipy.sparse.linalg.svds`` on the host, as the reference does (its ARPACK
    start vector is the one thing here that is not seeded by ``--seed``; pass ``embeddings=`` to
-   :func:`run` to use fixed ones);
+   :func:`run` to use fixed ones), or with ``--svd_backend device`` :func:`gdd.svd.svd_embeddings`
+   (fp64 subspace iteration on the device, seeded by ``--seed``);
 3. clustering (:158-181, :560-583): :func:`gdd.pipeline.kmeans_cluster` (device StandardScaler and
    KMeans / MiniBatchKMeans, bit-exact with scikit-learn);
 4. condensation (:184-201): :func:`gdd.recsys.build_condensed_bipartite` (device, bit-exact);
@@ -86,8 +87,15 @@ def build_interaction_matrix(num_users: int, num_items: int, u, i, values=None) 
     return sp.coo_matrix((v, (u, i)), shape=(num_users, num_items)).tocsr()
 
 
-def compute_svd_embeddings(R_: sp.csr_matrix, dim: int, seed: int = 42):
-    """Truncated SVD embeddings scaled by sqrt(S) (:124-155), on the host like the reference."""
+def compute_svd_embeddings(R_: sp.csr_matrix, dim: int, seed: int = 42, backend: str = "host"):
+    """Truncated SVD embeddings scaled by sqrt(S) (:124-155). ``backend="host"`` (default) is
+    ``scipy.sparse.linalg.svds`` like the reference; ``"device"`` is :func:`gdd.svd.svd_embeddings`
+    (fp64 block subspace iteration on the MI355X, a pure function of ``(R, dim, seed)``)."""
+    if backend == "device":
+        from .svd import svd_embeddings
+        return svd_embeddings(R_, dim, seed=seed)
+    if backend != "host":
+        raise ValueError(f"compute_svd_embeddings: backend must be 'host' or 'device', got {backend!r}")
     from scipy.sparse.linalg import svds
     k = min(dim, min(R_.shape) - 1)
     if k <= 0:
@@ -123,6 +131,8 @@ def parse_args(argv=None):
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--eval_topk", type=int, default=20)
     p.add_argument("--eval_max_users", type=int, default=5000)
+    p.add_argument("--svd_backend", type=str, default="host", choices=("host", "device"),
+                   help="SVD embeddings by scipy svds on the host (the reference's) or by gdd.svd on the device.")
     return p.parse_args(argv)
 
 
@@ -144,7 +154,8 @@ def run(args, out_root: str = "ClustGDD", embeddings=None, timings: Optional[dic
     print("[cluster] computing SVD embeddings...")
     t0 = time.perf_counter()
     if embeddings is None:
-        user_emb_np, item_emb_np = compute_svd_embeddings(R_train, dim=args.svd_dim, seed=args.seed)
+        user_emb_np, item_emb_np = compute_svd_embeddings(R_train, dim=args.svd_dim, seed=args.seed,
+                                                          backend=getattr(args, "svd_backend", "host"))
     else:
         user_emb_np, item_emb_np = embeddings
     tm["svd_s"] = time.perf_counter() - t0

@@ -513,6 +513,55 @@ int gdd_recall_at_k(int B, int64_t I, int k, float* scores, const int32_t* tr_pt
                     const int32_t* te_ptr, const int32_t* te_col, unsigned long long* hits,
                     gdd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- */
+/* (f1) the recommender's clustering embeddings. compute_svd_embeddings (distill_recsys.py:124-155):  */
+/* a truncated SVD of the interaction matrix, here a deterministic fp64 block subspace iteration     */
+/* with Rayleigh-Ritz (DESIGN.md "Device truncated SVD"; the loop is gdd/svd.py). Every matrix below  */
+/* is fp64 row-major with b <= gdd_svd_max_block() (128) columns. No entry point uses floating-point */
+/* atomics: two calls on the same input give the same bits.                                         */
+/* gdd_spmm_f64 (:124-155, the products behind svds): Y = A X, A CSR n_rows x n_cols with fp32       */
+/*   values (val NULL: all ones); each output element is one multiply-then-add chain from +0 in CSR  */
+/*   entry order (no fma); empty rows give zeros.                                                    */
+/* gdd_gram_f64 (:124-155): G = Wᵀ W (b x b, symmetric bit for bit). form: 0 = fp64 MFMA, 1 = plain  */
+/*   fp64 fma, -1 = the library's default. gdd_tsmm_f64 (:124-155): out = W Q, Q b x b, out != W.     */
+/* gdd_chol_inv_f64 (:124-155): G = Rᵀ R by Cholesky in one workgroup's LDS, Rinv = R⁻¹ (upper).      */
+/*   A pivot at or below b 2^-52 max diag(G) sets *flag (device int, never cleared here) to 1 and    */
+/*   gives Rinv = I. gdd_cholqr2_f64 (:124-155): V = orthonormal basis of Z's columns by two passes of*/
+/*   gram, chol_inv, tsmm (V may be Z); after a breakdown V is not orthonormal and *flag says so.    */
+/* gdd_svd_segment (:124-155): `steps` times W = A V, Z = Aᵀ W, V = CholeskyQR2(Z) with no host       */
+/*   synchronisation; A is n_big x n_small CSR, (rowptr_t, col_t, val_t) its transpose               */
+/*   (gdd_csr_transpose), V and Z n_small x b, W n_big x b.                                           */
+/* gdd_svd_residuals (:124-155): r[j] = ||Z_j - lam[j] V_j||_2 for j < k (lam: device, b values).      */
+/* gdd_svd_finalize (:124-155, :148-155 the sqrt(S) scaling): S[j] = sqrt(max(lam[j], 0)); the sign   */
+/*   of pair j makes the largest-magnitude entry of V_j positive (lowest row on ties); V_out          */
+/*   (n_small x k) = ±V_j, U_out (n_big x k) = ±W_j / S[j] (a zero column where S[j] == 0);           */
+/*   emb_small / emb_big (fp32) = those times sqrt(max(S[j], 1e-12)). Outputs but S are nullable;     */
+/*   sign: k doubles of scratch.                                                                     */
+/* ---------------------------------------------------------------------------------------------- */
+int gdd_svd_max_block(void);
+int gdd_spmm_f64(int64_t n_rows, int64_t n_cols, const int32_t* rowptr, const int32_t* col,
+                 const float* val, int b, const double* X, double* Y, gdd_stream_t stream);
+size_t gdd_gram_f64_ws_bytes(int64_t n_rows, int b);
+int gdd_gram_f64(int64_t n_rows, int b, const double* W, double* G, int form, void* ws, size_t ws_bytes,
+                 gdd_stream_t stream);
+int gdd_tsmm_f64(int64_t n_rows, int b, const double* W, const double* Q, double* out,
+                 gdd_stream_t stream);
+int gdd_chol_inv_f64(int b, const double* G, double* Rinv, int32_t* flag, gdd_stream_t stream);
+size_t gdd_cholqr2_ws_bytes(int64_t n_rows, int b);
+int gdd_cholqr2_f64(int64_t n_rows, int b, const double* Z, double* V, int32_t* flag, void* ws,
+                    size_t ws_bytes, gdd_stream_t stream);
+size_t gdd_svd_segment_ws_bytes(int64_t n_big, int64_t n_small, int b);
+int gdd_svd_segment(int64_t n_big, int64_t n_small, const int32_t* rowptr, const int32_t* col,
+                    const float* val, const int32_t* rowptr_t, const int32_t* col_t, const float* val_t,
+                    int b, int steps, double* V, double* W, double* Z, int32_t* flag, void* ws,
+                    size_t ws_bytes, gdd_stream_t stream);
+size_t gdd_svd_residuals_ws_bytes(int64_t n, int k);
+int gdd_svd_residuals(int64_t n, int b, int k, const double* Z, const double* V, const double* lam,
+                      double* r, void* ws, size_t ws_bytes, gdd_stream_t stream);
+int gdd_svd_finalize(int64_t n_small, int64_t n_big, int b, int k, const double* V, const double* W,
+                     const double* lam, double* S, double* V_out, double* U_out, float* emb_small,
+                     float* emb_big, double* sign, gdd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
