@@ -157,6 +157,12 @@ SIGNATURES = {
     "gdd_svd_residuals": (_c_int, [_c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
     "gdd_svd_finalize": (_c_int, [_c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
+    "gdd_rank_max_dim": (_c_int, []),
+    "gdd_rank_ws_bytes": (_c_size, [_c_i64, _c_int]),
+    "gdd_rank_rowpass": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_rank_wsum": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _c_size, _vp]),
 }
 
 _lib = None

@@ -562,6 +562,32 @@ int gdd_svd_finalize(int64_t n_small, int64_t n_big, int b, int k, const double*
                      const double* lam, double* S, double* V_out, double* U_out, float* emb_small,
                      float* emb_big, double* sign, gdd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- */
+/* The Rankformer teacher's layer (Rankformer/code/rec.py:143-274; DESIGN.md "Rankformer teacher").  */
+/* Both passes run over a CSR of n_rows x n_cols with nnz stored entries (int32 rowptr / col), fp32   */
+/* row-major tables of d columns, 1 <= d <= gdd_rank_max_dim() (256).                                 */
+/* gdd_rank_rowpass (rec.py:202-239): per row r and stored entry e = (r, c): s_out[e] = <Q_r, K_c>,   */
+/*   s_sum[r] = sum_e s_e, SK[r] = sum_e K_c, SV[r] = sum_e V_c, A[r] = sum_e s_e V_c. Q, s_sum, SK,   */
+/*   SV, A have n_rows rows, K and V n_cols rows.                                                     */
+/* gdd_rank_wsum (rec.py:135-137, :249-254): Y[r] = sum_e w[e] V_c; with a / b non-null also          */
+/*   ta[r] = sum_e a[e], tb[r] = sum_e b[e]. w, a, b are in this CSR's entry order (for a transposed   */
+/*   CSR the caller permutes them with gdd_csr_transpose's perm_out).                                 */
+/* Empty rows give zeros. A column outside [0, n_cols) is not read: it sets *bad (device int,          */
+/* nullable), contributes nothing, and its s_out is NaN. No floating-point atomics: the entries are   */
+/* cut into fixed chunks, one wave each, a row cut by a chunk end leaves partial sums in ws            */
+/* (gdd_rank_ws_bytes, shared by both passes) and a second launch adds them in chunk order, so the     */
+/* summation order depends on the CSR alone and two runs give the same bits.                          */
+/* ---------------------------------------------------------------------------------------------- */
+int gdd_rank_max_dim(void);
+size_t gdd_rank_ws_bytes(int64_t nnz, int d);
+int gdd_rank_rowpass(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* rowptr,
+                     const int32_t* col, int d, const float* Q, const float* K, const float* V,
+                     float* s_out, float* s_sum, float* SK, float* SV, float* A, int32_t* bad, void* ws,
+                     size_t ws_bytes, gdd_stream_t stream);
+int gdd_rank_wsum(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                  int d, const float* w, const float* V, const float* a, const float* b, float* Y,
+                  float* ta, float* tb, int32_t* bad, void* ws, size_t ws_bytes, gdd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
