@@ -359,8 +359,10 @@ extern "C" int gdd_rank_wsum(int64_t n_rows, int64_t n_cols, int64_t nnz, const 
   if (ws_bytes < gdd_rank_ws_bytes(nnz, d)) return fail(GDD_E_WORKSPACE, "rank_wsum: workspace too small");
   hipStream_t s = to_hip(stream);
   float* part = static_cast<float*>(ws);
-  float* ta_o = a ? ta : nullptr;
-  float* tb_o = b ? tb : nullptr;
+  // an edge array of no entries has no address (a caller's empty tensor is a null pointer): with
+  // nnz == 0 a row sum that was asked for is all zeros, not left unwritten
+  float* ta_o = (a || nnz == 0) ? ta : nullptr;
+  float* tb_o = (b || nnz == 0) ? tb : nullptr;
   if (nnz > 0) {
     const unsigned g = chunk_grid(nnz);
 #define GDD_WS(J)                                                                                  \

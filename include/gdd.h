@@ -571,7 +571,8 @@ int gdd_svd_finalize(int64_t n_small, int64_t n_big, int b, int k, const double*
 /*   SV, A have n_rows rows, K and V n_cols rows.                                                     */
 /* gdd_rank_wsum (rec.py:135-137, :249-254): Y[r] = sum_e w[e] V_c; with a / b non-null also          */
 /*   ta[r] = sum_e a[e], tb[r] = sum_e b[e]. w, a, b are in this CSR's entry order (for a transposed   */
-/*   CSR the caller permutes them with gdd_csr_transpose's perm_out).                                 */
+/*   CSR the caller permutes them with gdd_csr_transpose's perm_out). With nnz == 0 (an empty edge     */
+/*   array may be a null pointer) a non-null ta / tb is written all the same: zeros.                  */
 /* Empty rows give zeros. A column outside [0, n_cols) is not read: it sets *bad (device int,          */
 /* nullable), contributes nothing, and its s_out is NaN. No floating-point atomics: the entries are   */
 /* cut into fixed chunks, one wave each, a row cut by a chunk end leaves partial sums in ws            */

@@ -8,7 +8,14 @@ forward bound of a sum of that many fp32 terms in any order (deg the row's lengt
 product's; the factor 2 covers the second-order terms); Σ|terms| is computed in fp64 from absolute
 values (for A_r = Σ s_e V_c the terms are |q_f k_cf| |v_cg|). Layers: the largest absolute error
 against the fixture's fp64 output is at most 4 x the reference's own fp32 error on the same input
-(recorded in the fixture): the same sums in another order."""
+(recorded in the fixture): the same sums in another order.
+
+The kernel widths run from 1 to 256, so all four instantiations (one to four features per lane:
+d <= 64, 128, 192, 256) execute under the same kernel bound, the out-of-range column also at
+d = 193. The chunk geometry with poisoned buffers, the autograd functions against fp64 autograd
+(2 (Dmax + d + 4) 2^-24 Σ|terms|), the clamp, cut rows, d = 193 and stacked layers against the second
+fixture (4 x the reference's fp32 error), and a graph without pairs are in
+test_gpu_rankformer_edges.py, with their bounds in its docstring."""
 import os
 import sys
 
@@ -22,7 +29,7 @@ import rankformer_ref as R  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 U24 = 2.0 ** -24
-DIMS = [1, 8, 63, 64, 65, 128]
+DIMS = [1, 8, 63, 64, 65, 128, 129, 192, 193, 255, 256]  # one to four features per lane
 ROWS = 70
 
 
@@ -137,8 +144,16 @@ def test_width_above_the_limit_raises(csr):
 
 
 def test_out_of_range_column_sets_the_flag():
+    out_of_range_column(64)
+
+
+def test_out_of_range_column_sets_the_flag_four_features_per_lane():
+    out_of_range_column(193)
+
+
+def out_of_range_column(d):
     from gdd import rankformer as RF
-    n_cols, d = 50, 64
+    n_cols = 50
     rowptr, col, lens = make_csr(n_cols, False)
     rows = np.repeat(np.arange(ROWS), lens)
     hit = [int(rowptr[20]) + 5, int(rowptr[22]) + 64]  # inside a row, and a row's last entry

@@ -5,7 +5,13 @@ export's format.
 
 Bounds: the dense definition and the reference's linearised evaluation are the same function in
 fp64; on outputs of size 0.15 (gradients of size 1.4) their difference is a few ulps (measured
-7e-17 and 2.5e-15), so 1e-12 absolute separates rounding from any change of the definition."""
+7e-17 and 2.5e-15), so 1e-12 absolute separates rounding from any change of the definition. The
+second fixture (rankformer_layer_more.npz: the clamp at (alpha, clamp) = (0.5, 0.6) and (0.25, 0.3),
+the cut-row case, d = 193, two stacked layers) is held to the same 1e-12 (measured at most 2.6e-16
+and 5.9e-15), and its clamp cases to the conditions that make them worth running: each of the three
+clamped denominators is clamped on some rows and not on others, and none lies within 1e-4 of the
+clamp value (their fp32 error is about 1e-7; a kink that close would make the fp32 and fp64
+gradients differ legitimately)."""
 import os
 import sys
 import types
@@ -63,6 +69,80 @@ def test_dense_definition_gradient_equals_reference(case):
     err = float((x.grad - torch.from_numpy(case["g64"])).abs().max())
     print(f"dense gradient vs reference fp64: {err:.3e}")
     assert err <= ABS
+
+
+@pytest.fixture(scope="module", params=list(R.MORE_CASES))
+def more(request):
+    c = R.load_more_case(request.param)
+    c["M"] = R.mask_of(c["u"], c["i"], int(c["n"]), int(c["m"]))
+    return c
+
+
+def test_second_fixture_holds_what_it_is_for():
+    assert os.path.getsize(R.GOLDEN_MORE) < 2 ** 20
+    cut = R.load_more_case("cut_c05")
+    n, m = int(cut["n"]), int(cut["m"])
+    assert (n, m, cut["x"].shape) == (100, 80, (180, 65))
+    du, di = np.bincount(cut["u"], minlength=n), np.bincount(cut["i"], minlength=m)
+    assert du[0] == 0 and du[1] == m - 1 and di[0] == n - 1 and di[5] == 0
+    assert 0.1 < cut["u"].shape[0] / (n * m) < 0.25
+    # rows of both orientations span more than one 32-entry chunk
+    assert du.max() > 64 and di.max() > 96
+    assert R.load_more_case("small193")["x"].shape == (66, 193)
+    for name in R.MORE_CASES:
+        c = R.load_more_case(name)
+        assert c["z64"].dtype == c["g64"].dtype == np.float64 and c["z64"].shape == c["x"].shape == c["W"].shape
+        assert np.array_equal(c["x"], c["x"].astype(np.float32).astype(np.float64))
+        assert 0 < float(c["z32_err"]) < 1e-5 and 0 < float(c["g32_err"]) < 1e-4
+
+
+def test_dense_definition_equals_reference_on_the_second_fixture(more):
+    """Output and gradient at the clamp settings, on cut rows, at d = 193 and stacked twice."""
+    x = torch.from_numpy(more["x"]).requires_grad_(True)
+    z = R.dense_stack(x, more["M"], more["alpha"], more["clamp"], more["layers"])
+    (z * torch.from_numpy(more["W"])).sum().backward()
+    ez = float((z.detach() - torch.from_numpy(more["z64"])).abs().max())
+    eg = float((x.grad - torch.from_numpy(more["g64"])).abs().max())
+    print(f"{more['name']}: dense vs reference fp64: output {ez:.3e}, gradient {eg:.3e}")
+    assert ez <= ABS and eg <= ABS
+
+
+@pytest.mark.parametrize("name", [k for k, v in R.MORE_CASES.items() if v[2] > 0])
+def test_clamp_is_active_on_some_rows_and_no_denominator_sits_on_it(name):
+    """Each of the three denominators is clamped for at least one row and unclamped for at least
+    one, and none lies within 1e-4 of the clamp value (their fp32 error is about 1e-7)."""
+    more = R.load_more_case(name)
+    more["M"] = R.mask_of(more["u"], more["i"], int(more["n"]), int(more["m"]))
+    counts, gap = R.clamp_conditions(torch.from_numpy(more["x"]), more["M"], more["alpha"], more["clamp"])
+    print(f"{more['name']}: clamped (D_u, item sum of Omega+, item -sum of Omega-) = {counts}, closest {gap:.2e}")
+    assert all(0 < k < total for k, total in counts)
+    assert gap >= 1e-4
+
+
+def test_plain_passes_are_the_dense_sums():
+    """rankformer_ref's gather / index_add_ definitions of the two passes against dense matrix
+    products on the autograd tests' graph (fp64: a few ulps)."""
+    u, i, n, m = R.autograd_pairs()
+    M = R.mask_of(u, i, n, m)
+    deg_r, deg_c = M.sum(1), M.sum(0)
+    assert deg_c[0] == n - 1 and deg_r[3] == m - 1 and deg_r[5] == 0 and deg_c[7] == 0
+    assert 0.1 < len(u) / (n * m) < 0.25
+    g = torch.Generator().manual_seed(0)
+    Q, K, V = (torch.randn(r, 5, dtype=torch.float64, generator=g) for r in (n, m, m))
+    rows, col = torch.from_numpy(u), torch.from_numpy(i)
+    s, s_sum, SK, SV, A = R.plain_rowpass(rows, col, n, Q, K, V)
+    S = Q @ K.t()
+    for got, want in ((s, S[rows, col]), (s_sum, (M * S).sum(1)), (SK, M @ K), (SV, M @ V), (A, (M * S) @ V)):
+        assert float((got - want).abs().max()) <= ABS
+    w, a = torch.randn(len(u), dtype=torch.float64, generator=g), torch.randn(len(u), dtype=torch.float64, generator=g)
+    Wm = torch.zeros(n, m, dtype=torch.float64)
+    Wm[rows, col] = w
+    Y, ta, tb = R.plain_wsum(rows, col, n, w, V, a)
+    assert tb is None and float((Y - Wm @ V).abs().max()) <= ABS
+    Am = torch.zeros(n, m, dtype=torch.float64)
+    Am[rows, col] = a
+    assert float((ta - Am.sum(1)).abs().max()) <= ABS
+    assert [sum(p) for p in R.PATTERNS] == [0, 1, 31, 32, 33, 96, 96, 96, 96, 75, 100, 73]
 
 
 def test_duplicate_pairs_raise():
