@@ -183,6 +183,22 @@ __device__ __forceinline__ bool stopped(const int32_t* stop, int step_i) {
   return v != 0 && v - 1 < step_i;
 }
 
+// The ranking order of the recommender's top-k (gdd_recall_at_k, gdd_score_topk): a score and its
+// item id as one u64 whose integer order is "larger score first, equal scores by ascending item".
+// Never 0 for an item id below 2^31, so 0 serves as "no key".
+__device__ __forceinline__ uint64_t score_key(float v, int64_t j) {
+  uint32_t b = __float_as_uint(v);
+  b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // orderable: larger float -> larger key
+  return ((uint64_t)b << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)j);  // ties: lower index first
+}
+__device__ __forceinline__ float score_key_value(uint64_t key) {
+  const uint32_t b = (uint32_t)(key >> 32);
+  return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);
+}
+__device__ __forceinline__ int32_t score_key_item(uint64_t key) {
+  return (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
+}
+
 // sklearn _euclidean_dense_dense(a, b, n_features, squared=True) (_k_means_common.pyx:26-48):
 // groups of 4 summed left to right, added to the running result; remainder added one by one.
 // Separate mul/add (no fma).

@@ -196,12 +196,6 @@ __global__ void k_recall_mask(int B, int64_t I, const int32_t* __restrict__ tr_p
   for (int32_t e = tr_ptr[r] + threadIdx.x; e < tr_ptr[r + 1]; e += blockDim.x) row[tr_col[e]] = -1e9f;
 }
 
-__device__ __forceinline__ uint64_t score_key(float v, int64_t j) {
-  uint32_t b = __float_as_uint(v);
-  b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // orderable: larger float -> larger key
-  return ((uint64_t)b << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)j);  // ties: lower index first
-}
-
 __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {

@@ -228,7 +228,7 @@ int gdd_stream_copy(const void* src, void* dst, size_t bytes, gdd_stream_t strea
 
 const char* gdd_last_error(void) { return gdd::g_last_error.c_str(); }
 
-int gdd_abi_version(void) { return 2; }
+int gdd_abi_version(void) { return 3; }
 
 int gdd_spin_limit(void) { return gdd::kSpinLimit; }
 

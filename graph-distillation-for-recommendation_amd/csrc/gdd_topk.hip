@@ -1,0 +1,409 @@
+// gdd_topk.hip — ranked top-K recommendation lists and the ranking metrics computed from them
+// (Rankformer/code/model.py:252-343 evaluate: score GEMM, training mask, torch.topk; :27-53 test:
+// precision, recall, NDCG).
+//
+// gdd_score_topk never writes a score to memory. A workgroup of four waves owns 16 users, four per
+// wave. The item table streams through LDS in tiles of 64 rows (staged once for the 16 users), lane l
+// of every wave scores item l of the tile against the wave's four users, whose rows are read through
+// wave-uniform pointers (scalar loads: the user values are SGPR operands of the fmas and cost no LDS
+// bandwidth, which the per-lane item reads need); with d % 4 == 0 the next tile is fetched into
+// registers while the current one is scored. Each user keeps a running top-K:
+//   * thr, the K-th largest key seen at the last selection (0 before the first), and an append
+//     buffer of `cap` keys in LDS (cap = the power of two >= K + 64, at least 128);
+//   * a key above thr is appended (ballot + prefix count: the wave owns its users, no atomics);
+//   * when a further tile might not fit (cnt + 64 > cap) the wave sorts the buffer (bitonic,
+//     descending), keeps the first K and raises thr to the K-th.
+// Keys are unique (score_key holds the item id), so the final sorted K do not depend on arrival
+// order. The score of (user, item) is one fmaf chain over f = 0 .. d-1 from +0: float4 LDS reads of
+// the item row feed the chain in ascending f, the d % 4 tail is read one by one.
+//
+// gdd_rank_metrics: one wave per user finds the hit flag of every rank by binary search in the
+// user's sorted test row, one lane per cut-off sums DCG and IDCG in rank order in fp64; a second,
+// one-workgroup launch adds the users in a fixed order.
+#include <climits>
+
+#include "gdd_common.hpp"
+
+namespace gdd {
+namespace {
+
+constexpr int kTkThreads = 256;
+constexpr int kTkUW = 4;                              // users per wave
+constexpr int kTkUsers = kTkUW * (kTkThreads / 64);   // users per workgroup
+constexpr int kTkItems = 64;                          // items per tile: one per lane
+constexpr int kTkMaxK = 256;
+constexpr int kMaxDimTk = 256;                        // gdd_rank_max_dim()
+constexpr int kMetMaxNk = 8;
+
+// LDS traffic between the lanes of one wave: order it without a workgroup barrier
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// bitonic sort of buf[0 .. cap) (cap a power of two >= 128), descending, by one wave
+__device__ __forceinline__ void wave_sort_desc(uint64_t* buf, int cap, int lane) {
+  for (int k = 2; k <= cap; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < (cap >> 1); t += 64) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const int p = i | j;
+        const uint64_t a = buf[i], b = buf[p];
+        const bool swap = (i & k) == 0 ? a < b : a > b;
+        if (swap) {
+          buf[i] = b;
+          buf[p] = a;
+        }
+      }
+      wave_sync();
+    }
+  }
+}
+
+// sort the cnt appended keys, keep the K largest, raise the threshold to the K-th
+__device__ __forceinline__ void wave_select(uint64_t* buf, int cap, int K, int& cnt, uint64_t& thr, int lane) {
+  for (int t = cnt + lane; t < cap; t += 64) buf[t] = 0;  // below every key
+  wave_sync();
+  wave_sort_desc(buf, cap, lane);
+  if (cnt >= K) {
+    cnt = K;
+    thr = buf[K - 1];
+  }
+}
+
+// row stride of the LDS tables in floats: a multiple of 4 (float4 reads) with S/4 odd, so the eight
+// lanes of a ds_read_b128 group fall on distinct banks
+__host__ __device__ inline int tk_stride(int d) {
+  int s = (d + 3) & ~3;
+  if (((s >> 2) & 1) == 0) s += 4;
+  return s;
+}
+inline int tk_cap(int K) {
+  int c = 128;
+  while (c < K + kTkItems) c <<= 1;
+  return c;
+}
+inline size_t tk_lds(int d, int K) {
+  return sizeof(uint64_t) * kTkUsers * (size_t)tk_cap(K) + sizeof(float) * (size_t)kTkItems * tk_stride(d) +
+         sizeof(int32_t) * (kTkThreads + kTkUsers);
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// the thread's share of a tile of n4 float4 starting at src, into registers
+template <int NP>
+__device__ __forceinline__ void tk_fetch(f32x4 (&pre)[NP > 0 ? NP : 1], const float* __restrict__ src, int n4,
+                                         int tid) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+    if (tid + p * kTkThreads < n4) pre[p] = reinterpret_cast<const f32x4*>(src)[tid + p * kTkThreads];
+}
+
+// NP > 0: d % 4 == 0, V 16-byte aligned and a tile is at most NP float4 per thread: the next tile is
+// fetched into registers before the current one is scored, so its latency hides behind the scoring
+// and the top-K upkeep. NP == 0: any d and alignment, a tile is staged float by float.
+template <int NP>
+__global__ __launch_bounds__(kTkThreads) void k_score_topk(
+    int64_t B, int64_t I, int d, int K, int cap, const int32_t* __restrict__ users,
+    const float* __restrict__ U, int64_t nu, const float* __restrict__ V,
+    const int32_t* __restrict__ mask_ptr, const int32_t* __restrict__ mask_col, float mask_value,
+    int32_t* __restrict__ top_item, float* __restrict__ top_score, int32_t* __restrict__ bad) {
+  extern __shared__ __align__(16) unsigned char tk_smem[];
+  const int S = tk_stride(d);
+  uint64_t* s_keys = reinterpret_cast<uint64_t*>(tk_smem);       // kTkUsers x cap
+  float* s_v = reinterpret_cast<float*>(s_keys + (size_t)kTkUsers * cap);  // kTkItems x S
+  int32_t* s_flag = reinterpret_cast<int32_t*>(s_v + kTkItems * S);  // one per thread
+  int32_t* s_row = s_flag + kTkThreads;                          // U row of each user, -1: none
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b0 = (int64_t)blockIdx.x * kTkUsers;
+
+  if (tid < kTkUsers) {
+    const int64_t b = b0 + tid;
+    int32_t row = -1;
+    if (b < B) {
+      const int64_t r = users ? (int64_t)users[b] : b;
+      if (r >= 0 && r < nu) row = (int32_t)r;
+    }
+    s_row[tid] = row;
+  }
+  __syncthreads();
+
+  // the wave's users: liveness, mask rows (checked once: a column outside [0, I) kills the row)
+  bool live[kTkUW], dead[kTkUW];
+  int32_t cur[kTkUW], end[kTkUW];
+  int64_t nxt[kTkUW];  // the column at cur (wave-uniform), INT64_MAX past the row's end
+  int cnt[kTkUW];
+  uint64_t thr[kTkUW];
+#pragma unroll
+  for (int j = 0; j < kTkUW; ++j) {
+    const int ul = wave * kTkUW + j;
+    const int64_t b = b0 + ul;
+    live[j] = b < B;
+    dead[j] = live[j] && s_row[ul] < 0;
+    cur[j] = end[j] = 0;
+    nxt[j] = INT64_MAX;
+    cnt[j] = 0;
+    thr[j] = 0;
+    if (live[j] && mask_ptr) {
+      cur[j] = mask_ptr[b];
+      end[j] = mask_ptr[b + 1];
+      bool out = false;
+      for (int32_t e = cur[j] + lane; e < end[j]; e += 64) {
+        const int32_t c = mask_col[e];
+        out |= c < 0 || c >= I;
+      }
+      if (__ballot(out)) dead[j] = true;
+      if (cur[j] < end[j]) nxt[j] = mask_col[cur[j]];
+    }
+    if (dead[j] && bad && lane == 0) atomicAdd(bad, 1);
+  }
+
+  const float* vrow = s_v + lane * S;
+  // the wave's user rows through wave-uniform pointers: scalar loads, no LDS traffic for them
+  const float* ug[kTkUW];
+#pragma unroll
+  for (int j = 0; j < kTkUW; ++j) {
+    const int32_t row = __builtin_amdgcn_readfirstlane(s_row[__builtin_amdgcn_readfirstlane(wave) * kTkUW + j]);
+    ug[j] = U + (int64_t)(row >= 0 ? row : 0) * d;  // no valid row: row 0 stands in, the list is dropped
+  }
+  const int d4 = d & ~3;
+  const int q = d >> 2;  // float4 per row
+  f32x4 pre[NP > 0 ? NP : 1];
+  int pre_off[NP > 0 ? NP : 1];  // LDS float offset of the thread's p-th float4 of a tile
+  if (NP > 0) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int idx = tid + p * kTkThreads, r = idx / q;
+      pre_off[p] = r * S + 4 * (idx - r * q);
+    }
+    tk_fetch<NP>(pre, V, (int)(I < kTkItems ? I : kTkItems) * q, tid);
+  }
+  for (int64_t i0 = 0; i0 < I; i0 += kTkItems) {
+    const int rows = (int)(I - i0 < kTkItems ? I - i0 : kTkItems);
+    __syncthreads();  // the previous tile has been scored
+    if (NP > 0) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+        if (tid + p * kTkThreads < rows * q) *reinterpret_cast<f32x4*>(s_v + pre_off[p]) = pre[p];
+      if (i0 + kTkItems < I) {
+        const int64_t left = I - i0 - kTkItems;
+        tk_fetch<NP>(pre, V + (i0 + kTkItems) * d, (int)(left < kTkItems ? left : kTkItems) * q, tid);
+      }
+    } else {
+      const float* src = V + i0 * d;
+      for (int idx = tid; idx < rows * d; idx += kTkThreads) {
+        const int r = idx / d, f = idx - r * d;
+        s_v[r * S + f] = src[idx];
+      }
+    }
+    __syncthreads();
+    const int64_t item = i0 + lane;
+    const int64_t tile_end = i0 + kTkItems;
+    float acc[kTkUW];
+#pragma unroll
+    for (int j = 0; j < kTkUW; ++j) acc[j] = 0.f;
+    if (lane < rows) {
+      for (int f = 0; f < d4; f += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(vrow + f);
+#pragma unroll
+        for (int j = 0; j < kTkUW; ++j) {
+          const float* u = ug[j] + f;
+          float a = acc[j];
+          a = __builtin_fmaf(u[0], v.x, a);
+          a = __builtin_fmaf(u[1], v.y, a);
+          a = __builtin_fmaf(u[2], v.z, a);
+          a = __builtin_fmaf(u[3], v.w, a);
+          acc[j] = a;
+        }
+      }
+      for (int f = d4; f < d; ++f) {
+        const float v = vrow[f];
+#pragma unroll
+        for (int j = 0; j < kTkUW; ++j) acc[j] = __builtin_fmaf(ug[j][f], v, acc[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kTkUW; ++j) {
+      if (!live[j]) continue;  // wave-uniform
+      uint64_t* buf = s_keys + (size_t)(wave * kTkUW + j) * cap;
+      bool masked = false;
+      if (nxt[j] < tile_end) {  // wave-uniform
+        s_flag[tid] = 0;
+        wave_sync();
+        for (;;) {
+          const int32_t e = cur[j] + lane;
+          const int64_t c = e < end[j] ? (int64_t)mask_col[e] : (int64_t)INT64_MAX;
+          const bool in = c < tile_end;
+          if (in && c >= i0) s_flag[wave * 64 + (int)(c - i0)] = 1;
+          const int n = __popcll(__ballot(in));
+          cur[j] += n;
+          if (n < 64) break;
+        }
+        wave_sync();
+        masked = s_flag[tid] != 0;
+        wave_sync();
+        nxt[j] = cur[j] < end[j] ? (int64_t)mask_col[cur[j]] : (int64_t)INT64_MAX;
+      }
+      if (cnt[j] + kTkItems > cap) wave_select(buf, cap, K, cnt[j], thr[j], lane);
+      const uint64_t key = score_key(masked ? mask_value : acc[j], item);
+      const bool cand = lane < rows && key > thr[j];
+      const uint64_t bal = __ballot(cand);
+      if (cand) buf[cnt[j] + __popcll(bal & ((1ull << lane) - 1ull))] = key;
+      cnt[j] += __popcll(bal);
+    }
+  }
+
+#pragma unroll
+  for (int j = 0; j < kTkUW; ++j) {
+    if (!live[j]) continue;
+    const int64_t b = b0 + wave * kTkUW + j;
+    uint64_t* buf = s_keys + (size_t)(wave * kTkUW + j) * cap;
+    wave_select(buf, cap, K, cnt[j], thr[j], lane);
+    for (int r = lane; r < K; r += 64) {
+      const uint64_t key = buf[r];
+      top_item[b * K + r] = dead[j] ? -1 : score_key_item(key);
+      if (top_score) top_score[b * K + r] = dead[j] ? __builtin_nanf("") : score_key_value(key);
+    }
+  }
+}
+
+// per_user[b] = (precision, recall, ndcg) x nk of user b's list; one wave per user
+constexpr int kMetThreads = 256;
+__global__ __launch_bounds__(kMetThreads) void k_rank_metrics(
+    int64_t B, int K, const int32_t* __restrict__ top_item, const int32_t* __restrict__ te_ptr,
+    const int32_t* __restrict__ te_col, const int32_t* __restrict__ te_deg, int nk,
+    const int32_t* __restrict__ topks, const double* __restrict__ inv_log2, double* __restrict__ per_user) {
+  __shared__ uint64_t s_hit[kMetThreads / 64][kTkMaxK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.x * (kMetThreads / 64) + wave;
+  if (b >= B) return;
+  const int32_t beg = te_ptr[b], fin = te_ptr[b + 1];
+  const int64_t n = te_deg ? (int64_t)te_deg[b] : (int64_t)(fin - beg);
+  for (int g = 0; g < kTkMaxK / 64; ++g) {
+    const int r = g * 64 + lane;
+    bool hit = false;
+    if (r < K && n > 0) {
+      const int32_t item = top_item[b * K + r];
+      int32_t lo = beg, hi = fin;
+      while (lo < hi) {
+        const int32_t mid = (int32_t)(((int64_t)lo + hi) >> 1);
+        if (te_col[mid] < item) lo = mid + 1; else hi = mid;
+      }
+      hit = lo < fin && te_col[lo] == item;
+    }
+    const uint64_t bal = __ballot(hit);
+    if (lane == 0) s_hit[wave][g] = bal;
+  }
+  wave_sync();
+  if (lane < nk) {
+    const int k = topks[lane] < 1 ? 1 : (topks[lane] > K ? K : topks[lane]);  // never past the list
+    double pre = 0.0, rec = 0.0, ndcg = 0.0;
+    if (n > 0) {
+      const int64_t cut = n < k ? n : (int64_t)k;
+      int hits = 0;
+      double dcg = 0.0, idcg = 0.0;
+      for (int r = 0; r < k; ++r) {
+        if ((s_hit[wave][r >> 6] >> (r & 63)) & 1ull) {
+          ++hits;
+          dcg += inv_log2[r];
+        }
+        if (r < cut) idcg += inv_log2[r];
+      }
+      pre = (double)hits / (double)k;
+      rec = (double)hits / (double)cut;
+      ndcg = dcg / idcg;
+    }
+    double* o = per_user + b * 3 * nk;
+    o[lane] = pre;
+    o[nk + lane] = rec;
+    o[2 * nk + lane] = ndcg;
+  }
+}
+
+// sums[c] = sum over users of per_user[b][c], c < 3 nk, in a fixed order: thread t adds users
+// t, t + 256, ... in ascending order, then a pairwise tree over the 256 partial sums
+__global__ __launch_bounds__(kMetThreads) void k_rank_metric_sums(
+    int64_t B, int nc, const double* __restrict__ per_user, const int32_t* __restrict__ te_ptr,
+    const int32_t* __restrict__ te_deg, double* __restrict__ sums, int64_t* __restrict__ count) {
+  __shared__ double s_part[kMetThreads];
+  __shared__ long long s_cnt[kMetThreads];
+  const int tid = threadIdx.x;
+  for (int c = 0; c <= nc; ++c) {  // c == nc: the count
+    double a = 0.0;
+    long long m = 0;
+    for (int64_t b = tid; b < B; b += kMetThreads) {
+      if (c < nc) {
+        a += per_user[b * nc + c];
+      } else {
+        const int64_t n = te_deg ? (int64_t)te_deg[b] : (int64_t)(te_ptr[b + 1] - te_ptr[b]);
+        m += n > 0 ? 1 : 0;
+      }
+    }
+    s_part[tid] = a;
+    s_cnt[tid] = m;
+    __syncthreads();
+    for (int o = kMetThreads / 2; o > 0; o >>= 1) {
+      if (tid < o) {
+        s_part[tid] = s_part[tid] + s_part[tid + o];
+        s_cnt[tid] += s_cnt[tid + o];
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      if (c < nc) sums[c] = s_part[0];
+      else count[0] = (int64_t)s_cnt[0];
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+}  // namespace gdd
+
+using namespace gdd;
+
+extern "C" int gdd_score_topk(int64_t B, int64_t I, int d, int K, const int32_t* users, const float* U,
+                              int64_t nu, const float* V, const int32_t* mask_ptr, const int32_t* mask_col,
+                              float mask_value, int32_t* top_item, float* top_score, int32_t* bad,
+                              gdd_stream_t stream) {
+  GDD_REQUIRE(B >= 0 && B < INT32_MAX && I >= 1 && I < INT32_MAX && nu >= 1 && nu < INT32_MAX,
+              "score_topk: B=%lld I=%lld nu=%lld unsupported", (long long)B, (long long)I, (long long)nu);
+  GDD_REQUIRE(d >= 1 && d <= kMaxDimTk, "score_topk: d=%d outside [1, %d]", d, kMaxDimTk);
+  GDD_REQUIRE(K >= 1 && K <= kTkMaxK && K <= I, "score_topk: K=%d outside [1, min(%d, I=%lld)]", K, kTkMaxK,
+              (long long)I);
+  if (B == 0) return GDD_OK;
+  GDD_REQUIRE(U && V && top_item, "score_topk: null pointer");
+  GDD_REQUIRE(!mask_ptr || mask_col, "score_topk: mask_ptr without mask_col");
+  const size_t lds = tk_lds(d, K);
+  const bool vec = (d & 3) == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0;
+  auto kern = !vec ? k_score_topk<0> : d <= 64 ? k_score_topk<4> : d <= 128 ? k_score_topk<8> : k_score_topk<16>;
+  if (lds > 65536)
+    GDD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const unsigned grid = (unsigned)((B + kTkUsers - 1) / kTkUsers);
+  kern<<<grid, kTkThreads, lds, to_hip(stream)>>>(B, I, d, K, tk_cap(K), users, U, nu, V, mask_ptr, mask_col,
+                                                  mask_value, top_item, top_score, bad);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+extern "C" int gdd_rank_metrics(int64_t B, int K, const int32_t* top_item, const int32_t* te_ptr,
+                                const int32_t* te_col, const int32_t* te_deg, int nk, const int32_t* topks,
+                                const double* inv_log2, double* per_user, double* sums, int64_t* count,
+                                gdd_stream_t stream) {
+  GDD_REQUIRE(B >= 0 && B < INT32_MAX && K >= 1 && K <= kTkMaxK && nk >= 1 && nk <= kMetMaxNk,
+              "rank_metrics: B=%lld K=%d nk=%d unsupported", (long long)B, K, nk);
+  GDD_REQUIRE(topks && inv_log2 && sums && count && (B == 0 || (top_item && te_ptr && per_user)),
+              "rank_metrics: null pointer");
+  hipStream_t s = to_hip(stream);
+  if (B > 0) {
+    const unsigned grid = (unsigned)((B + kMetThreads / 64 - 1) / (kMetThreads / 64));
+    k_rank_metrics<<<grid, kMetThreads, 0, s>>>(B, K, top_item, te_ptr, te_col, te_deg, nk, topks, inv_log2,
+                                                per_user);
+    GDD_LAUNCHED();
+  }
+  k_rank_metric_sums<<<1, kMetThreads, 0, s>>>(B, 3 * nk, per_user, te_ptr, te_deg, sums, count);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}

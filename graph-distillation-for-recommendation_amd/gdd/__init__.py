@@ -21,18 +21,22 @@ the reference file:line each entry point replaces):
 * :mod:`gdd.rankformer` — the Rankformer teacher: :class:`RankformerLayer` / :class:`GCNLayer` as
   fused row passes without float atomics, :class:`RankformerTeacher`, ``rankformer.train_teacher``
   and :func:`save_teacher` (the file ``distill_recsys --teacher_path`` loads); the command line is
-  :mod:`gdd.train_teacher`
+  :mod:`gdd.train_teacher` (``--select_by ndcg``: the reference's selection on validation NDCG)
+* :mod:`gdd.rankeval` — :func:`recommend` (ranked top-K lists from a fused score + top-K kernel that
+  never writes a score), :func:`rank_metrics` and :class:`RankingEvaluator` (precision, recall and
+  NDCG@K as the reference teacher computes them)
 * :mod:`gdd.agent` / :mod:`gdd.agent_induct` — the transductive and inductive ClustGDD agents;
   :mod:`gdd.train_clustgdd_transduct` / :mod:`gdd.train_clustgdd_induct` /
   :mod:`gdd.distill_recsys` — the drop-in command lines
 """
 from . import _lib  # noqa: F401  (imports torch first, see _lib docstring)
-from . import gcn, pipeline, rankformer, recsys  # noqa: F401
+from . import gcn, pipeline, rankeval, rankformer, recsys  # noqa: F401
 from .cluster import argmax_rows, cluster_mean, group_by_label
 from .condense import ER_estimator, attaw_ER_estimator, graph_compress, graph_sparse
 from .graph import (CSRGraph, induced_subgraph, normalize_adj, normalize_adj_tensor, propagate, spmm,
                     to_csr)
 from .kmeans import KMeans, MiniBatchKMeans
+from .rankeval import RankingEvaluator, rank_metrics, recommend
 from .rankformer import GCNLayer, InteractionGraph, RankformerLayer, RankformerTeacher, save_teacher
 from .sharded import ShardedKMeans, shard_rows
 from .svd import svd_embeddings, truncated_svd
@@ -43,4 +47,5 @@ __all__ = [
     "induced_subgraph", "group_by_label", "graph_sparse", "graph_compress", "ER_estimator", "attaw_ER_estimator",
     "truncated_svd", "svd_embeddings",
     "InteractionGraph", "RankformerLayer", "GCNLayer", "RankformerTeacher", "save_teacher",
+    "recommend", "rank_metrics", "RankingEvaluator",
 ]

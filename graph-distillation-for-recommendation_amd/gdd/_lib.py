@@ -163,6 +163,9 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _c_size, _vp]),
     "gdd_rank_wsum": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_score_topk": (_c_int, [_c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_f32, _vp,
+                                _vp, _vp, _vp]),
+    "gdd_rank_metrics": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -20,6 +20,11 @@ Stage by stage (reference line ranges):
    :func:`gdd.recsys.manual_adam_step`, :class:`gdd.recsys.RecallEvaluator` (device);
 7. artefacts (:735-764): :func:`gdd.recsys.save_distilled`.
 
+``--report_ranking`` (not in the reference; without it stdout is the reference's) adds, after the
+refinement, NDCG / recall / precision of the refined condensed model over the evaluated test users
+by :class:`gdd.rankeval.RankingEvaluator`, and with ``--teacher_path`` the same for the teacher's raw
+embeddings.
+
 The reference falls back to the CPU when no GPU is visible; this driver has no CPU path.
 """
 from __future__ import annotations
@@ -133,6 +138,10 @@ def parse_args(argv=None):
     p.add_argument("--eval_max_users", type=int, default=5000)
     p.add_argument("--svd_backend", type=str, default="host", choices=("host", "device"),
                    help="SVD embeddings by scipy svds on the host (the reference's) or by gdd.svd on the device.")
+    p.add_argument("--report_ranking", action="store_true",
+                   help="after refinement print NDCG / recall / precision at --report_topks of the refined "
+                        "condensed model (and of the teacher's raw embeddings) over the evaluated test users")
+    p.add_argument("--report_topks", type=str, default=None, help="cut-offs of --report_ranking (default: [eval_topk])")
     return p.parse_args(argv)
 
 
@@ -250,6 +259,22 @@ def run(args, out_root: str = "ClustGDD", embeddings=None, timings: Optional[dic
             print(f"[refine] ep={ep:04d} loss={loss.item():.6f} Recall@{args.eval_topk}={r:.6f}")
     torch.cuda.synchronize()
     tm["refine_s"] = time.perf_counter() - t0
+
+    if getattr(args, "report_ranking", False):
+        from .rankeval import RankingEvaluator, format_metrics, parse_topks
+        topks = parse_topks(args.report_topks) if getattr(args, "report_topks", None) else (int(args.eval_topk),)
+        ranking = RankingEvaluator(R_train, ds.test_u, ds.test_i, topks, device, mask_value=-1e9,
+                                   max_users=args.eval_max_users)
+        model.eval()
+        with torch.no_grad():
+            cu_z, ci_z = model.propagate()
+            m = ranking(cu_z[u2cu_t], ci_z[i2ci_t])
+        for line in format_metrics(topks, m):
+            print(f"[rank] condensed ({m['users']} users): {line}")
+        if args.teacher_path is not None:
+            m = ranking(tu, ti)
+            for line in format_metrics(topks, m):
+                print(f"[rank] teacher ({m['users']} users): {line}")
 
     out_dir = os.path.join(out_root, "distilled_recsys", args.dataset)
     R.save_distilled(out_dir, model, u2cu, i2ci, num_cu, num_ci)

@@ -28,10 +28,14 @@ than ``(n+m) × d`` or the number of interactions is allocated (the reference ma
   (main.py:219-227). The command line is :mod:`gdd.train_teacher`.
 
 Not offered: the contrastive loss (``--use_cl``), the three ablation switches (``--del_neg``,
-``--del_benchmark``, ``--del_omega_norm``), NDCG and precision (validation is Recall@K by
-:class:`gdd.recsys.RecallEvaluator`), and the reference's random trajectory: the device RNG stream
-differs from the reference's, results are deterministic for a seed on one device. There is no CPU
-path.
+``--del_benchmark``, ``--del_omega_norm``), and the reference's random trajectory: the device RNG
+stream differs from the reference's, results are deterministic for a seed on one device. There is no
+CPU path.
+
+Validation is Recall@K by :class:`gdd.recsys.RecallEvaluator` by default; ``select_by="ndcg"`` is the
+reference's loop (main.py:100-120): precision, recall and NDCG at ``topks`` by
+:class:`gdd.rankeval.RankingEvaluator`, the epoch kept is the one with the best validation
+NDCG@max(topks), and the test split is evaluated at every new best.
 """
 from __future__ import annotations
 
@@ -435,15 +439,30 @@ def train_teacher(num_users: int, num_items: int, train_u, train_i, valid_u, val
                   hidden_dim: int = 64, learning_rate: float = 0.1, reg_lambda: float = 1e-4,
                   loss_batch_size: int = 0, max_epochs: int = 2000, valid_interval: int = 20,
                   stopping_step: int = 10, topk: int = 20, seed: int = 12345, device="cuda", log=None,
-                  drop_repeats: bool = False, **model_kwargs):
+                  drop_repeats: bool = False, select_by: str = "recall", topks=None, test_u=None, test_i=None,
+                  **model_kwargs):
     """main.py:141-190 with parse.py's defaults: Adam, full-batch BPR (``loss_batch_size = 0``) or
     shuffled mini-batches, validation every ``valid_interval`` epochs by Recall@``topk`` over all
     validation users (:class:`gdd.recsys.RecallEvaluator`), stop after ``stopping_step`` validations
     without a new best, and restore the best epoch's weights. Returns ``(model, history)``;
     ``history`` has ``loss`` (per epoch), ``valid`` ([(epoch, recall)]), ``best_epoch``,
     ``best_recall``. Repeated training pairs raise ``ValueError`` unless ``drop_repeats`` keeps one
-    of each (the shipped Ali-Display split repeats 5,296 of its 121,178 lines)."""
+    of each (the shipped Ali-Display split repeats 5,296 of its 121,178 lines).
+
+    ``select_by="ndcg"`` follows main.py:100-120 instead: every validation computes precision, recall
+    and NDCG at ``topks`` (default ``[topk]``) over all validation users with
+    :class:`gdd.rankeval.RankingEvaluator` and logs them in the reference's wording, the epoch kept
+    is the one whose NDCG@max(topks) is strictly greater than every earlier one (starting from 0, as
+    the reference does), and ``test_u`` / ``test_i`` (optional) are evaluated at each new best.
+    ``history`` then has ``valid`` as [(epoch, metrics dict)], ``test`` (the metrics at the best
+    epoch, or None), ``best_ndcg`` and ``best_epoch``. The early stop is the same."""
     from .recsys import RecallEvaluator
+
+    if select_by not in ("recall", "ndcg"):
+        raise ValueError(f"train_teacher: select_by must be 'recall' or 'ndcg', got {select_by!r}")
+    if select_by == "ndcg":
+        from .rankeval import check_topks
+        topks = check_topks(topks if topks is not None else [topk], int(num_items))
 
     if not torch.cuda.is_available():
         raise RuntimeError("gdd.rankformer: no HIP device visible (the MI355X path has no CPU fallback)")
@@ -458,6 +477,9 @@ def train_teacher(num_users: int, num_items: int, train_u, train_i, valid_u, val
     graph = InteractionGraph(train_u, train_i, num_users, num_items, dev)
     model = RankformerTeacher(graph, hidden_dim=hidden_dim, seed=seed, **model_kwargs)
     opt = torch.optim.Adam(model.parameters(), lr=learning_rate)
+    if select_by == "ndcg":
+        return _train_select_ndcg(model, graph, opt, valid_u, valid_i, test_u, test_i, topks, reg_lambda,
+                                  loss_batch_size, max_epochs, valid_interval, stopping_step, seed, say)
     evaluator = RecallEvaluator(graph.to_scipy(), valid_u, valid_i, topk, dev, max_users=max(1, int(num_users)))
     shuffle = torch.Generator(device=dev)
     shuffle.manual_seed(int(seed) + 1)
@@ -510,6 +532,80 @@ def train_teacher(num_users: int, num_items: int, train_u, train_i, valid_u, val
     graph.check()
     history = {"loss": [float(x) for x in torch.stack(losses).cpu()] if losses else [],
                "valid": valid_hist, "best_epoch": best_epoch, "best_recall": best}
+    return model, history
+
+
+def _train_select_ndcg(model, graph, opt, valid_u, valid_i, test_u, test_i, topks, reg_lambda,
+                       loss_batch_size, max_epochs, valid_interval, stopping_step, seed, say):
+    """train_teacher's loop with the reference's model selection (main.py:73-134, :161-190)."""
+    from .rankeval import RankingEvaluator, format_metrics
+
+    dev = graph.device
+    R_train = graph.to_scipy()
+    valid_eval = RankingEvaluator(R_train, valid_u, valid_i, topks, dev)
+    test_eval = RankingEvaluator(R_train, test_u, test_i, topks, dev) if test_u is not None else None
+    shuffle = torch.Generator(device=dev)
+    shuffle.manual_seed(int(seed) + 1)
+
+    def evaluate(ev) -> dict:
+        model.eval()
+        with torch.no_grad():
+            users, items = model.computer()
+            m = ev(users, items)
+        model.train()
+        graph.check()
+        return m
+
+    def one_batch(u, i):
+        users, items = model.computer()
+        loss = model.loss_bpr(users, items, u, i, reg_lambda)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        return loss.detach()
+
+    state = {"ndcg": 0.0, "epoch": 0, "weights": copy.deepcopy(model.state_dict()), "test": None}
+    valid_hist = []
+
+    def validate(epoch: int) -> bool:
+        m = evaluate(valid_eval)
+        valid_hist.append((epoch, m))
+        say(f"[teacher] ----- epoch {epoch} validation -----")
+        for line in format_metrics(topks, m):
+            say(f"[teacher] {line}")
+        if not float(m["ndcg"][-1]) > state["ndcg"]:
+            return False
+        state.update(ndcg=float(m["ndcg"][-1]), epoch=epoch, weights=copy.deepcopy(model.state_dict()))
+        if test_eval is not None:
+            state["test"] = evaluate(test_eval)
+            say(f"[teacher] ===== test result (at {epoch} epoch) =====")
+            for line in format_metrics(topks, state["test"]):
+                say(f"[teacher] {line}")
+        return True
+
+    validate(0)
+    losses: List[torch.Tensor] = []
+    model.train()
+    E = graph.E
+    for epoch in range(1, int(max_epochs) + 1):
+        if loss_batch_size == 0:
+            losses.append(one_batch(graph.train_u, graph.train_i))
+        else:
+            order = torch.randperm(E, generator=shuffle, device=dev)
+            u_s, i_s = graph.train_u[order], graph.train_i[order]
+            parts = [one_batch(u_s[b:b + loss_batch_size], i_s[b:b + loss_batch_size])
+                     for b in range(0, E, int(loss_batch_size))]
+            losses.append(torch.stack(parts).mean())
+        if epoch % int(valid_interval) == 0:
+            say(f"[teacher] epoch {epoch} loss={float(losses[-1]):.6f}")
+            if not validate(epoch) and epoch - state["epoch"] >= int(stopping_step) * int(valid_interval):
+                say(f"[teacher] early stop at epoch {epoch}; best epoch {state['epoch']}")
+                break
+    model.load_state_dict(state["weights"])
+    graph.check()
+    history = {"loss": [float(x) for x in torch.stack(losses).cpu()] if losses else [],
+               "valid": valid_hist, "test": state["test"], "best_epoch": state["epoch"],
+               "best_ndcg": state["ndcg"], "topks": list(topks)}
     return model, history
 
 

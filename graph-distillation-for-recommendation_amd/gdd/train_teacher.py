@@ -11,7 +11,11 @@ Flags keep the reference's names and defaults where the reference has them (``--
 ``--stopping_step``, ``--seed``). The Rankformer layers are on unless ``--no_rankformer`` is given
 (``--use_rankformer`` is accepted and changes nothing); ``--data_dir`` / ``--dataset`` are
 ``gdd.distill_recsys``'s. Repeated lines of ``train.txt`` are dropped with a note (the layer is
-defined over distinct pairs). See :mod:`gdd.rankformer` for what is not offered.
+defined over distinct pairs). ``--select_by ndcg --topks "[20]"`` is the reference's model selection
+(main.py:100-120): precision, recall and NDCG at every cut-off of ``--topks`` per validation, the epoch
+with the best validation NDCG@max(topks) is kept, and the test split is reported at each new best.
+The default, ``--select_by recall``, selects on Recall@``--eval_topk``. See :mod:`gdd.rankformer` for
+what is not offered.
 """
 from __future__ import annotations
 
@@ -23,6 +27,7 @@ import time
 import torch
 
 from .distill_recsys import load_rankformer_dataset
+from .rankeval import format_metrics, parse_topks
 from .rankformer import save_teacher, train_teacher
 
 
@@ -52,7 +57,16 @@ def parse_args(argv=None):
     p.add_argument("--valid_interval", type=int, default=20)
     p.add_argument("--stopping_step", type=int, default=10)
     p.add_argument("--eval_topk", type=int, default=20)
-    return p.parse_args(argv)
+    p.add_argument("--select_by", type=str, default="recall", choices=("recall", "ndcg"),
+                   help="recall: Recall@eval_topk; ndcg: the reference's NDCG@max(topks) with the test split "
+                        "reported at each new best")
+    p.add_argument("--topks", type=str, default="[20]", help="cut-offs of --select_by ndcg, e.g. \"[20, 50]\"")
+    args = p.parse_args(argv)
+    try:
+        args.topks = list(parse_topks(args.topks))
+    except (ValueError, SyntaxError) as e:
+        p.error(f"--topks: {e}")
+    return args
 
 
 def run(args):
@@ -68,14 +82,24 @@ def run(args):
         hidden_dim=args.hidden_dim, learning_rate=args.learning_rate, reg_lambda=args.reg_lambda,
         loss_batch_size=args.loss_batch_size, max_epochs=args.max_epochs, valid_interval=args.valid_interval,
         stopping_step=args.stopping_step, topk=args.eval_topk, seed=args.seed, device=device, log=print,
-        drop_repeats=True,
+        drop_repeats=True, select_by=args.select_by, topks=args.topks if args.select_by == "ndcg" else None,
+        test_u=ds.test_u if args.select_by == "ndcg" else None,
+        test_i=ds.test_i if args.select_by == "ndcg" else None,
         use_gcn=args.use_gcn, gcn_layers=args.gcn_layers, gcn_left=args.gcn_left, gcn_right=args.gcn_right,
         gcn_mean=args.gcn_mean, use_rankformer=not args.no_rankformer, rankformer_layers=args.rankformer_layers,
         rankformer_tau=args.rankformer_tau, rankformer_alpha=args.rankformer_alpha,
         rankformer_clamp_value=args.rankformer_clamp_value)
     torch.cuda.synchronize()
-    print(f"[teacher] {len(hist['loss'])} epochs in {time.perf_counter() - t0:.1f} s; best epoch "
-          f"{hist['best_epoch']} Recall@{args.eval_topk}={hist['best_recall']:.6f}")
+    if args.select_by == "ndcg":
+        print(f"[teacher] {len(hist['loss'])} epochs in {time.perf_counter() - t0:.1f} s; best epoch "
+              f"{hist['best_epoch']} ndcg@{args.topks[-1]}={hist['best_ndcg']:.6f}")
+        if hist["test"] is not None:
+            print(f"[teacher] ===== test result (at {hist['best_epoch']} epoch) =====")
+            for line in format_metrics(args.topks, hist["test"]):
+                print(f"[teacher] {line}")
+    else:
+        print(f"[teacher] {len(hist['loss'])} epochs in {time.perf_counter() - t0:.1f} s; best epoch "
+              f"{hist['best_epoch']} Recall@{args.eval_topk}={hist['best_recall']:.6f}")
     out_dir = os.path.dirname(os.path.abspath(args.out))
     os.makedirs(out_dir, exist_ok=True)
     save_teacher(args.out, model)

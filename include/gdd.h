@@ -589,6 +589,40 @@ int gdd_rank_wsum(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* ro
                   int d, const float* w, const float* V, const float* a, const float* b, float* Y,
                   float* ta, float* tb, int32_t* bad, void* ws, size_t ws_bytes, gdd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- */
+/* Ranked top-K lists and the ranking metrics (Rankformer/code/model.py:252-343 evaluate: score     */
+/* GEMM, training mask, torch.topk; :27-53 test: precision, recall, NDCG; DESIGN.md "Ranked top-K").  */
+/* gdd_score_topk (model.py:304-317): for b < B, user row r = users[b] (users NULL: r = b) of U      */
+/*   (nu x d, nu >= 1) against all I rows of V (I x d), 1 <= d <= gdd_rank_max_dim(), 1 <= K <= 256, */
+/*   K <= I < 2^31, B >= 0 (B == 0 returns without a launch). The score s(u, i) is the fp32 chain    */
+/*   s = fmaf(U[r,f], V[i,f], s) over f = 0 .. d-1 ascending, starting from +0: a function of the    */
+/*   two rows alone, the same bits whatever B, users, K or the item's place in a tile. An item       */
+/*   listed in the user's mask row (mask_ptr / mask_col: CSR of B rows in the order of the call,     */
+/*   columns ascending; mask_ptr NULL: no mask) is not removed, its score is mask_value (the         */
+/*   reference's -1024, model.py:313), so masked items fill the tail when K exceeds the unmasked.    */
+/*   top_item[b, 0 .. K) are the items in descending score, equal scores in ascending item id (the   */
+/*   order of gdd_recall_at_k); top_score (nullable) their scores, the bits above. A user id outside */
+/*   [0, nu) or a mask column outside [0, I) is not dereferenced: *bad (device int, nullable, not    */
+/*   cleared here) is incremented once for that row and the row is all -1 (top_score NaN). No score  */
+/*   is written to memory, no workspace, no floating-point atomics: two runs give the same bits.     */
+/* gdd_rank_metrics (model.py:27-53): per user b with n = te_deg[b] (te_deg NULL: the row length;     */
+/*   the reference counts repeated lines of the split, dataloader.py:65-70) and per cut-off          */
+/*   k = topks[j] (device, nk <= 8 ascending values in [1, K]; an entry outside is clamped):         */
+/*   hits = |top_item[b, :k] ∩ row b| by binary search in te_ptr / te_col (B rows, ascending,         */
+/*   distinct), precision = hits / k, recall = hits / min(n, k) (the reference's clamp, :43-47),     */
+/*   ndcg = (sum_{r<k} hit_r inv_log2[r]) / (sum_{r<min(n,k)} inv_log2[r]), both sums in rank order; */
+/*   inv_log2 (device, K doubles) = 1 / log2(r + 2) from the host. All fp64. per_user is             */
+/*   B x 3 x nk (precision, recall, ndcg); a user with n == 0 gets zeros. sums (3 x nk) adds the     */
+/*   users in a fixed order (a second one-workgroup launch; no atomics), count (device int64) is the */
+/*   number of users with n > 0: the reference's means are sums / count.                             */
+/* ---------------------------------------------------------------------------------------------- */
+int gdd_score_topk(int64_t B, int64_t I, int d, int K, const int32_t* users, const float* U, int64_t nu,
+                   const float* V, const int32_t* mask_ptr, const int32_t* mask_col, float mask_value,
+                   int32_t* top_item, float* top_score, int32_t* bad, gdd_stream_t stream);
+int gdd_rank_metrics(int64_t B, int K, const int32_t* top_item, const int32_t* te_ptr, const int32_t* te_col,
+                     const int32_t* te_deg, int nk, const int32_t* topks, const double* inv_log2,
+                     double* per_user, double* sums, int64_t* count, gdd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
