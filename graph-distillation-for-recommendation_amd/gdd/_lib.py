@@ -40,6 +40,8 @@ SIGNATURES = {
     "gdd_propagate_relabeled_ws_bytes": (_c_size, [_c_i64, _c_i64, _c_int]),
     "gdd_propagate_relabeled": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_int, _vp, _c_int, _c_f32,
                                          _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_community_order_ws_bytes": (_c_size, [_c_i64, _c_i64]),
+    "gdd_community_order": (_c_int, [_c_i64, _c_i64, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _c_size, _vp]),
     "gdd_spmm": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_int, _c_f32, _vp, _vp, _vp, _c_f32,
                           _vp, _c_size, _vp]),
     "gdd_spmm_plan": (_c_int, [_c_i64, _c_i64, _vp, _c_int, _vp, _c_size, _vp]),

@@ -58,7 +58,8 @@ class ClustGDD:
         labels = torch.LongTensor(np.asarray(data.labels_full)).to(dev)
         idx_train = data.idx_train
         adj_norm = normalize_adj(g)                                                 # :46-50
-        target_feat, _ = propagate(adj_norm, features, args.prop_num, args.alpha)   # :55-65
+        target_feat, _ = propagate(adj_norm, features, args.prop_num, args.alpha,   # :55-65
+                                   relabel=getattr(args, "relabel", None))
         model = MLP(nfeat=target_feat.shape[-1], nhid=args.hidden, dropout=args.predropout,
                     weight_decay=args.prewd, nlayers=args.prenlayers, lr=args.prelr,
                     with_relu=False, with_bn=False, nclass=data.nclass, device=dev).to(dev)

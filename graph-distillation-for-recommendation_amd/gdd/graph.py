@@ -172,13 +172,43 @@ def _ws_propagate(adj: CSRGraph, d: int):
     return lib, _lib.workspace(lib.gdd_propagate_ws_bytes(adj.n, adj.nnz, d), adj.device)
 
 
-def locality_order(adj: CSRGraph, kind: str = "degree") -> torch.Tensor:
+def _community_order(adj: CSRGraph, sweeps: int):
+    """gdd_community_order: (rho, labels, changed), all int32 on the graph's device."""
+    sweeps = int(sweeps)
+    if sweeps < 0:
+        raise ValueError("sweeps must be >= 0")
+    lib = _lib.device_lib()
+    dev = adj.device
+    n = adj.n
+    rho = torch.empty(n, dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    changed = torch.empty(sweeps, dtype=torch.int32, device=dev)
+    ws = _lib.workspace(lib.gdd_community_order_ws_bytes(n, adj.nnz), dev)
+    _lib.check(lib.gdd_community_order(n, adj.nnz, adj.rowptr.data_ptr(), _lib.ptr(adj.col), sweeps,
+                                       rho.data_ptr(), labels.data_ptr(), changed.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+    return rho, labels, changed
+
+
+def community_labels(adj: CSRGraph, sweeps: int = 12):
+    """The labels behind ``locality_order(adj, "community", sweeps)`` and the number of labels each
+    sweep changed (0 from the fixed point on), both int32 on the graph's device, for inspection."""
+    _, labels, changed = _community_order(adj, sweeps)
+    return labels, changed
+
+
+def locality_order(adj: CSRGraph, kind: str = "degree", sweeps: int = 12) -> torch.Tensor:
     """A node relabelling for :func:`propagate`'s ``relabel`` (rho: node r's row of the intermediate
     hops at rho[r], int32 on the graph's device). ``"degree"``: rows by descending length, ties by id
     (the hubs every hop gathers most sit together); ``"rcm"``: reverse Cuthill-McKee of the pattern
-    (scipy, on the host), which recovers the community blocks of a graph whose ids were shuffled."""
+    (scipy, on the host), which recovers the community blocks of a graph whose ids were shuffled;
+    ``"community"``: ``sweeps`` sweeps of deterministic label propagation on the device
+    (gdd_community_order), nodes sorted by (label, id), which groups such blocks without leaving the
+    GPU. ``sweeps`` is ignored by the other kinds."""
     dev = adj.device
     n = adj.n
+    if kind == "community":
+        return _community_order(adj, sweeps)[0]
     if kind == "degree":
         deg = (adj.rowptr[1:] - adj.rowptr[:-1]).to(torch.int64)
         order = torch.sort(-deg, stable=True).indices
@@ -203,7 +233,7 @@ def propagate(adj_norm: CSRGraph, features: torch.Tensor, T: int, alpha: float, 
     :func:`gdd.sharded.propagation_shards_pay` says the gathers outweigh a per-hop all-gather
     (ogbn-products, not ogbn-arxiv), the rows are partitioned over the ranks
     (:func:`gdd.sharded.sharded_propagate`, bit-identical); otherwise every rank propagates.
-    ``relabel`` (opt-in): ``"degree"``, ``"rcm"`` or a permutation rho (node r -> row rho[r]): the
+    ``relabel`` (opt-in): ``"degree"``, ``"rcm"``, ``"community"`` or a permutation rho (node r -> row rho[r]): the
     intermediate hops run in that node order (gdd_propagate_relabeled) — same bits, different
     gather locality.
     """

@@ -70,6 +70,9 @@ def parser():
     p.add_argument("--data_dir", type=str, default="", help="GraphSAINT-format dataset directory")
     p.add_argument("--device", type=str, default="", help="cuda:<gpu_id> by default")
     p.add_argument("--json", type=str, default="", help="write accuracy + timings as JSON here")
+    # absent unless given (SUPPRESS), so the printed Namespace of a default run is what it was
+    p.add_argument("--relabel", choices=["degree", "rcm", "community"], default=argparse.SUPPRESS,
+                   help="node order of the propagation's intermediate hops (same bits; gdd.propagate)")
     return p
 
 

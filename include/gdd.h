@@ -96,6 +96,24 @@ int gdd_propagate_relabeled(int64_t n, int64_t nnz, const int32_t* rowptr, const
                             const float* val, const int32_t* rho, int d, const float* X, int T,
                             float alpha, float* target, float* p_last, float* p_tmp, void* ws,
                             size_t ws_bytes, gdd_stream_t stream);
+/* A community node order for that rho: deterministic synchronous label propagation over the CSR     */
+/* structure (values ignored), CAP = 256. deg[v] = rowptr[v+1] - rowptr[v]; labels start as lab[v] = */
+/* v. A sweep reads the previous sweep's labels and writes a second buffer: row r collects one vote  */
+/* for lab[r] itself (whether or not the diagonal is stored) and one vote for lab[c] of each of its  */
+/* first min(deg[r], CAP) stored entries c with c != r and deg[c] <= CAP (an entry that points at a  */
+/* hub casts no vote); its new label is the one with the most votes, among equals the smallest. All  */
+/* counts are integers: no rounding, no dependence on scheduling. After `sweeps` sweeps, order = the */
+/* nodes sorted by (final label, node id) and rho[order[j]] = j. A sweep that changes nothing is a   */
+/* fixed point: the sweeps after it are skipped on the device (same answer, no host round trip).     */
+/* labels (nullable, n): the final labels. changed (nullable, int32[sweeps]): labels changed per     */
+/* sweep; skipped sweeps write 0. n = 0 and nnz = 0 are valid (the identity). n < 0, nnz < 0,        */
+/* sweeps < 0 and a short workspace are rejected on the host. A rowptr pair outside [0, nnz] makes   */
+/* its row empty and an out-of-range column casts no vote; neither is dereferenced, both set a flag  */
+/* the call reads back (one stream synchronise at its end) and reports as GDD_E_INVALID.             */
+size_t gdd_community_order_ws_bytes(int64_t n, int64_t nnz);
+int gdd_community_order(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* col, int sweeps,
+                        int32_t* rho, int32_t* labels, int32_t* changed, void* ws, size_t ws_bytes,
+                        gdd_stream_t stream);
 /* one hop: y = (scale * Â) @ x with the canonical order above; if acc != NULL also                   */
 /*   acc = acc + acc_scale * y  (two fp32 roundings, no contraction).                               */
 int gdd_spmm(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* col, const float* val,
