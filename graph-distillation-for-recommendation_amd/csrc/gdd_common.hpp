@@ -97,6 +97,8 @@ bool bf16q_norms_fit(int dim, int k);
 // GDD_FORCE (tests and diagnostics only): a comma-separated list of tokens, each forcing a path that
 // other shapes take by default (so its bits can be pinned on a small shape), e.g.
 // GDD_FORCE=kpp_no_table,lloyd_no_prune or GDD_FORCE=kpp_big1_max=32768. Read on every call (host).
+// The kpp_* tokens are read in one place, kpp_plan (gdd_kmeanspp.hip), which turns them into the
+// launch path that gdd_kmeans_plusplus_path names.
 //   kpp_no_table      k-means++ without the n x n distance table (small and multi-block plans)
 //   kpp_force_table   the multi-block table although kpp_table_pays says no (small k)
 //   kpp_no_big1       the per-block table rounds instead of one workgroup per trial (n <= 16,384)

@@ -2069,7 +2069,8 @@ struct StepWs {
   float* sq[2];
   float* inertia;
 };
-StepWs carve_step(void* ws, size_t ws_bytes, int64_t b, int k) {
+// the step's buffers carved from ws; with a null ws only measured (*bytes: the workspace they need)
+StepWs carve_step(void* ws, size_t ws_bytes, int64_t b, int k, size_t* bytes = nullptr) {
   Carver cv(ws, ws_bytes);
   StepWs w;
   w.keys[0] = cv.take<unsigned long long>(b);
@@ -2078,6 +2079,7 @@ StepWs carve_step(void* ws, size_t ws_bytes, int64_t b, int k) {
   w.sq[0] = cv.take<float>(b);
   w.sq[1] = cv.take<float>(b);
   w.inertia = cv.take<float>(1);
+  if (bytes) *bytes = cv.off + 1024;
   return w;
 }
 }  // namespace
@@ -2085,9 +2087,9 @@ StepWs carve_step(void* ws, size_t ws_bytes, int64_t b, int k) {
 extern "C" size_t gdd_minibatch_state_bytes(void) { return sizeof(MBState); }
 
 extern "C" size_t gdd_minibatch_step_ws_bytes(int64_t b, int k) {
-  const size_t bb = (size_t)std::max<int64_t>(b, 1);
-  return 2 * align256(sizeof(unsigned long long) * bb) + align256(sizeof(float) * (size_t)std::max(k, 1)) +
-         2 * align256(sizeof(float) * bb) + align256(sizeof(float)) + 1024;
+  size_t bytes = 0;
+  carve_step(nullptr, 0, std::max<int64_t>(b, 1), std::max(k, 1), &bytes);
+  return bytes;
 }
 
 extern "C" int gdd_minibatch_step(int64_t b, int dim, const float* X, const int64_t* rows, int k,

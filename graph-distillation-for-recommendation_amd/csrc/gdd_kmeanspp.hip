@@ -329,10 +329,10 @@ __device__ double skl_dot(const double* __restrict__ c, const float* __restrict_
   }
 }
 
-// does every element of the chunk with m rows take the plain k-ordered chain? (the per-chunk form of
-// the host's skl_all_seq: a call whose last chunk is small runs edge kernels there, but its other
-// chunks stay plain)
-__device__ __forceinline__ bool skl_chunk_seq(const SklPlan& p, int64_t m) {
+// does every element of the chunk with m rows take the plain k-ordered chain? (the host's
+// skl_all_seq asks it of every chunk of a call: a call whose last chunk is small runs edge kernels
+// there, but its other chunks stay plain)
+__host__ __device__ __forceinline__ bool skl_chunk_seq(const SklPlan& p, int64_t m) {
   if (p.T == 1 || p.dim > 384 || m <= 1) return false;
   const double mnk = (double)m * p.T * p.dim;
   if (mnk <= 1e6 && m * p.T <= 1200 && p.dim >= 32) return false;
@@ -3402,16 +3402,10 @@ int64_t skl_batch_size(int64_t nx, int64_t ny, int dim) {  // pairwise.py _eucli
 
 // true when every element of a call with T candidate rows takes the plain chain
 bool skl_all_seq(int64_t n, int T, int dim, int64_t B) {
-  if (T == 1 || dim > 384) return false;
-  int64_t ms[2] = {std::min(n, B), n > B ? n % B : 0};
-  for (int64_t m : ms) {
-    if (m <= 0) continue;
-    if (m == 1) return false;
-    const double mnk = (double)m * T * dim;
-    if (mnk <= 1e6 && m * T <= 1200 && dim >= 32) return false;
-    const bool threaded = kBlasThreads >= 2 && mnk >= 524288.0;
-    if (!threaded && m > 192 && T >= 12 && (m & 7) != 0) return false;
-  }
+  const SklPlan p{n, B, T, dim, 0, 0};
+  const int64_t ms[2] = {std::min(n, B), n > B ? n % B : 0};  // the full chunks' size, the last one's
+  for (int64_t m : ms)
+    if (m > 0 && !skl_chunk_seq(p, m)) return false;
   return true;
 }
 
@@ -3434,17 +3428,45 @@ extern "C" int gdd_skl_sqdist(int n_rows, const float* C, int64_t n, int dim, co
   return GDD_OK;
 }
 
-size_t kpp_ws_bytes(int64_t n, int dim, int n_trials, int k);
+// ---- k-means++ on the host: one plan, one workspace layout, one launcher per path ------------------
+// (k-means++, has the path table)
+namespace {
 
-// k (centres) sizes the fused rounds' arrival counters and gates the tables. This query bounds it
-// by n (an upper bound for every k); gdd_kmeans_plusplus_ws_bytes_k sizes for the caller's k
-extern "C" size_t gdd_kmeans_plusplus_ws_bytes(int64_t n, int dim, int n_trials) {
-  return kpp_ws_bytes(n, dim, n_trials, (int)std::min<int64_t>(n, INT_MAX));
-}
+enum KppPath {
+  KPP_FIRST_ONLY,         // k == 1
+  KPP_SINGLE_TABLE_PAIR,  // k_kpp1_dm2 chain under replay_or_run
+  KPP_SINGLE_TABLE,       // k_kpp1_dm
+  KPP_SINGLE_FUSED,       // k_kpp1_fused<SEQ>
+  KPP_SINGLE_TWO_LAUNCH,  // k_kpp1_dist<SEQ> + k_kpp1_pick
+  KPP_SPLIT,              // k_kpp_round<true, true> + k_kpp_dists<T>
+  KPP_BIG_PAIR,           // k_kpp1_big2<8>
+  KPP_BIG,                // k_kpp1_big<EPT>
+  KPP_BLOCK_TABLE,        // k_kpp_round<true> with a.D set
+  KPP_BLOCK,              // k_kpp_round<SEQ> (+ k_kpp_pot1 when T == 1)
+};
 
-extern "C" size_t gdd_kmeans_plusplus_ws_bytes_k(int64_t n, int dim, int n_trials, int k) {
-  return kpp_ws_bytes(n, dim, n_trials, std::max(1, k));
-}
+// Everything the host decides about one seeding, from (n, dim, T, k) and GDD_FORCE alone.
+struct KppPlan {
+  int64_t n, nblk;  // points; 4096-point blocks
+  int dim, T, k;    // each at least 1 (the size queries take any value)
+  KppPath path;
+  bool seq;         // every distance of the rounds takes the plain chain (SklPlan::all_seq)
+  int64_t B, B1;    // skl_batch_size of the rounds' calls (T candidate rows), of the first centre's
+  int exact;        // cum_tol's mode (diagnostic): GDD_KPP_EXACT=0 never replays (tests only), 2 always replays
+  int overlap;      // the pair chain's two folds overlapped (kpp1_fold_pair); GDD_FORCE=kpp_pair_serial: 0
+  int ept;          // k_kpp1_big's entries per thread: 8, 16 or 32
+  size_t lds;       // k_kpp_init, k_kpp_round: the candidate row (fp64), the block's distances + chain read-ahead
+  size_t lds1;      // k_kpp1_dist
+  size_t lds_split;  // k_kpp_dists
+  size_t lds_big;   // k_kpp1_big, k_kpp1_big2
+  // the optional buffers. They follow (n, dim, T, k), not the path: a forced path keeps its workspace
+  bool xt;              // X^T (dim x n)
+  bool xt_before_init;  // ... transposed before k_kpp_init and read through KppArgs (multi-block)
+  bool xt_after_first;  // ... transposed after the first centre and read through Kpp1Args (single-block)
+  bool Dbig;            // the multi-block n x n table, and with it the rounds' block prefixes (pfx)
+  bool Dm;              // the single-block n x n table
+  bool pairs;           // the two-rounds-per-launch buffers (dist2, potv2, candw2, candself2)
+};
 
 // the multi-block rounds read their distances from an n x n table when every distance is the plain
 // chain (slot-independent) and the table is affordable: n <= kDmBigMax (4 GiB), dim <= kDmX, k >=
@@ -3453,62 +3475,426 @@ constexpr int64_t kDmBigMax = 32768;
 // largest n for k_kpp1_big (one workgroup per trial): beyond ~16K points one CU's share of the row
 // traffic (two rows in, one out per round) outweighs the per-block rounds' extra launch work
 // (Ali-Display users, 17,730 points: 35.2 vs 23.5 us per round); GDD_FORCE=kpp_big1_max=N overrides
-int64_t kpp_big1_max() {
-  const int64_t v = (int64_t)forced_value("kpp_big1_max", 16384);
-  return v < kBig1Max ? v : kBig1Max;
-}
+constexpr int64_t kBig1Default = 16384;
 // the table costs n^2 dim fp64 fmas once (~0.45 ms at 6,040 x 64, i.e. ~5e12 fma/s) and saves each
 // of the k - 1 rounds its distance phase (>= ~5 us per round beyond 4096 points): build it only when
 // (k - 1) x 5 us covers n^2 dim / 5e12 s, i.e. (k - 1) 2.5e7 >= n^2 dim (k = 20 at
 // n = 32,768 would build a 4 GiB table for 19 rounds). ML-1M users (6,040 x 64, k = 604): 1.5e10 >=
 // 2.3e9; Ali-Display users (17,730 x 64, k = 1,773): 4.4e10 >= 2.0e10
 bool kpp_table_pays(int64_t n, int dim, int k) {
-  return (double)(k - 1) * 2.5e7 >= (double)n * (double)n * (double)std::max(dim, 1);
+  return (double)(k - 1) * 2.5e7 >= (double)n * (double)n * (double)dim;
 }
-bool kpp_big_table(int64_t n, int dim, int T, int k) {
-  if (n <= kBlk || n > kDmBigMax || dim > kDmX || T < 2 || k < kDmMinK) return false;
-  if (forced("kpp_no_table")) return false;
-  if (!kpp_table_pays(n, dim, k) && !forced("kpp_force_table")) return false;
-  return skl_all_seq(n, T, dim, skl_batch_size(T, n, dim));
+
+// The one place that reads GDD_FORCE's kpp_* tokens and GDD_KPP_EXACT.
+KppPlan kpp_plan(int64_t n, int dim_in, int n_trials, int k_in) {
+  KppPlan p{};
+  const int dim = p.dim = std::max(dim_in, 1);
+  const int T = p.T = std::max(n_trials, 1);
+  const int k = p.k = std::max(k_in, 1);
+  p.n = n;
+  p.nblk = (n + kBlk - 1) / kBlk;
+  p.B = skl_batch_size(T, n, dim);
+  p.B1 = skl_batch_size(1, n, dim);
+  p.seq = skl_all_seq(n, T, dim, p.B);
+  const char* ex = getenv("GDD_KPP_EXACT");
+  p.exact = ex ? atoi(ex) : 1;
+  p.overlap = forced("kpp_pair_serial") ? 0 : 1;
+  p.ept = n <= (int64_t)kBigThr * 8 ? 8 : n <= (int64_t)kBigThr * 16 ? 16 : 32;
+  p.lds = sizeof(double) * (size_t)dim + sizeof(float) * (kBlk + kChainPad);
+  p.lds1 = sizeof(double) * (size_t)T * std::max(dim, 48);
+  p.lds_split = sizeof(double) * (size_t)T * dim + sizeof(float) * (size_t)T * kBlk;
+  p.lds_big = sizeof(float) * ((size_t)kBigThr * p.ept + kChainPad);
+
+  const bool no_table = forced("kpp_no_table"), single_round = forced("kpp_single_round");
+  // a table: at most kDmX features, built from kDmMinK centres on. The single-block one (n <= 4096,
+  // at most 64 MiB) whenever it fits; the multi-block one where it pays and every chain is plain
+  const bool table_shape = dim <= kDmX && T >= 2 && k >= kDmMinK;
+  p.xt = n <= kBlk || n * (int64_t)dim < INT_MAX;
+  p.Dm = n <= kBlk && table_shape;
+  p.Dbig = n > kBlk && n <= kDmBigMax && table_shape && !no_table &&
+           (kpp_table_pays(n, dim, k) || forced("kpp_force_table")) && p.seq;
+  // two rounds per launch: T <= kPairMaxT; the 1024-thread rounds only at the 8-entry segments
+  // (n <= 8192: at 16 and 32 entries two folds in one kernel spill)
+  p.pairs = p.Dm || (p.Dbig && T <= kPairMaxT && n <= (int64_t)kBigThr * 8);
+
+  const bool single = p.nblk == 1 && T >= 2;
+  p.xt_before_init = p.xt && n > kBlk;
+  p.xt_after_first = single && p.seq && k > 1;
+  // one 1024-thread workgroup per trial (k_kpp1_big); GDD_FORCE=kpp_no_big1 keeps the per-block rounds
+  const int64_t big1_max = std::min((int64_t)forced_value("kpp_big1_max", (double)kBig1Default), kBig1Max);
+  const bool big1 = n <= big1_max && T >= 2 && !forced("kpp_no_big1");
+  // the split path has one workgroup per 4096-point block: it pays only when there are enough
+  // blocks to fill the chip (products' 2.45M points: 598 blocks). With few blocks the per-(block,
+  // trial) rounds win (6,040 points: 22 vs 69 us per round; 40,000: 47 vs 84).
+  const bool split = p.seq && p.xt_before_init && T >= 2 && T <= kSplitMaxT && p.lds_split <= 150 * 1024 &&
+                     p.nblk >= kSplitMinBlocks && !forced("kpp_no_split");
+  if (k == 1) {
+    p.path = KPP_FIRST_ONLY;
+  } else if (single) {
+    // the distance table pays once the rounds it saves (~3 us each) cover its one-off build; else one
+    // fused launch per round while its grid stays within 256 workgroups and a row within kMaxDimF
+    const int64_t fused_grid = (n + kFPts - 1) / kFPts * T;
+    if (p.seq && p.Dm && !no_table)
+      p.path = T <= kPairMaxT && !single_round ? KPP_SINGLE_TABLE_PAIR : KPP_SINGLE_TABLE;
+    else if (dim <= kMaxDimF && fused_grid <= 256 && !forced("kpp_two_launch"))
+      p.path = KPP_SINGLE_FUSED;
+    else
+      p.path = KPP_SINGLE_TWO_LAUNCH;
+  } else if (split) {
+    p.path = KPP_SPLIT;
+  } else if (p.Dbig && p.xt_before_init) {
+    p.path = !big1 ? KPP_BLOCK_TABLE : p.pairs && !single_round ? KPP_BIG_PAIR : KPP_BIG;
+  } else {
+    p.path = KPP_BLOCK;
+  }
+  return p;
 }
-// the single-block table (n <= 4096, at most 64 MiB): built from kDmMinK centres on
-bool kpp_small_table(int64_t n, int dim, int T, int k) {
-  return n <= kBlk && dim <= kDmX && T >= 2 && k >= kDmMinK;
+
+const char* kpp_path_name(const KppPlan& p) {
+  switch (p.path) {
+    case KPP_FIRST_ONLY: return "first_only";
+    case KPP_SINGLE_TABLE_PAIR: return "single_table_pair";
+    case KPP_SINGLE_TABLE: return "single_table";
+    case KPP_SINGLE_FUSED: return p.seq ? "single_fused/seq" : "single_fused/blas";
+    case KPP_SINGLE_TWO_LAUNCH: return p.seq ? "single_two_launch/seq" : "single_two_launch/blas";
+    case KPP_SPLIT: return "split";
+    case KPP_BIG_PAIR: return "big_pair";
+    case KPP_BIG: return "big";
+    case KPP_BLOCK_TABLE: return "block_table";
+    case KPP_BLOCK: return p.seq ? "block/seq" : "block/blas";
+  }
+  return "invalid";
 }
-// the 1024-thread table rounds two per launch (k_kpp1_big2; T <= kPairMaxT, the 8-entry segments,
-// n <= 8192: at 16 and 32 entries two folds in one kernel spill): workspace for the pairs
-bool kpp_big_pairs(int64_t n, int dim, int T, int k) {
-  return T <= kPairMaxT && n <= (int64_t)kBigThr * 8 && kpp_big_table(n, dim, T, k);
+
+// ---- the workspace: carved on the caller's buffer by the launcher, measured on a null base by the
+// queries. The buffers that only the host names; the others go straight into the kernels' arguments
+struct KppBufs {
+  KppState* st;
+  double* xsq;
+  float* closest0;
+  double* fsum0;
+  float* XT;
+  float* Dbig;
+  float* Dm;
+};
+
+void kpp_carve(const KppPlan& p, Carver& cv, KppBufs* bf, KppArgs* a, Kpp1Args* b1) {
+  const size_t n = (size_t)p.n, nblk = (size_t)p.nblk, T = (size_t)p.T;
+  bf->st = cv.take<KppState>(1);
+  bf->xsq = cv.take<double>(n);
+  bf->closest0 = cv.take<float>(n);
+  bf->fsum0 = cv.take<double>(nblk);
+  for (int q = 0; q < 2; ++q) a->dist[q] = cv.take<float>(n * T);
+  for (int q = 0; q < 2; ++q) a->vblk[q] = cv.take<float>(nblk * T);
+  for (int q = 0; q < 2; ++q) a->fsum[q] = cv.take<double>(nblk * T);
+  for (int q = 0; q < 2; ++q) a->cand[q] = cv.take<int64_t>(kMaxTrials);
+  a->pot1 = cv.take<float>(2);
+  a->winq = cv.take<int>(2);
+  for (int q = 0; q < 2; ++q) b1->potv[q] = cv.take<float>(T);
+  for (int q = 0; q < 2; ++q) b1->candw[q] = cv.take<int64_t>(T * T);
+  for (int q = 0; q < 2; ++q) b1->candself[q] = cv.take<int64_t>(T);
+  for (int q = 0; q < 2; ++q) b1->candr[q] = cv.take<int64_t>(T);
+  for (int q = 0; q < 2; ++q) b1->candn[q] = cv.take<double>(T);
+  b1->win = cv.take<int>(2);
+  b1->counter = cv.take<unsigned>((size_t)p.k * T);  // rounds c < k, trial t
+  bf->XT = p.xt ? cv.take<float>(n * (size_t)p.dim) : nullptr;
+  bf->Dbig = p.Dbig ? cv.take<float>(n * n) : nullptr;
+  // the per-block table rounds keep each round's block prefixes for the next round's count (r05);
+  // every other path's rounds must see nullptr here (k_kpp_round recomputes them)
+  for (int q = 0; q < 2; ++q) {
+    double* pfx = p.Dbig ? cv.take<double>(n * T) : nullptr;
+    a->pfx[q] = p.path == KPP_BLOCK_TABLE ? pfx : nullptr;
+  }
+  bf->Dm = p.Dm ? cv.take<float>(n * n) : nullptr;
+  if (p.pairs) {
+    for (int q = 0; q < 2; ++q) {
+      b1->dist2[q] = cv.take<float>(T * T * n);
+      b1->potv2[q] = cv.take<float>(T * T);
+      b1->candw2[q] = cv.take<int64_t>(T * T * T);
+      b1->candself2[q] = cv.take<int64_t>(T * T);
+    }
+  }
 }
 
 size_t kpp_ws_bytes(int64_t n, int dim, int n_trials, int k) {
-  const size_t T = (size_t)std::max(n_trials, 1);
-  const size_t nblk = (size_t)((n + kBlk - 1) / kBlk);
-  size_t b = 0;
-  b += align256(sizeof(KppState));
-  b += align256(sizeof(double) * n);          // xsq
-  b += align256(sizeof(float) * n);           // closest0
-  b += align256(sizeof(double) * nblk);       // fsum0
-  b += 2 * align256(sizeof(float) * n * T);   // dist ping-pong
-  b += 2 * align256(sizeof(float) * nblk * T);    // vblk
-  b += 2 * align256(sizeof(double) * nblk * T);   // fsum
-  b += 2 * align256(sizeof(int64_t) * kMaxTrials);
-  b += align256(sizeof(float) * 2);           // pot1
-  b += align256(sizeof(int) * 2);             // winq
-  b += 2 * align256(sizeof(float) * T);       // potv
-  b += 2 * align256(sizeof(int64_t) * T * T); // candw
-  b += 2 * align256(sizeof(int64_t) * T);     // candself
-  b += 2 * align256(sizeof(int64_t) * T) + 2 * align256(sizeof(double) * T);  // candr, candn
-  b += align256(sizeof(int) * 2) + align256(sizeof(unsigned) * (size_t)std::max(k, 1) * T);  // counters
-  if (n <= kBlk || (int64_t)n * std::max(dim, 1) < INT_MAX)
-    b += align256(sizeof(float) * n * (size_t)std::max(dim, 1));  // XT
-  if (kpp_big_table(n, dim, (int)T, k))
-    b += align256(sizeof(float) * n * n) + 2 * align256(sizeof(double) * n * T);  // table, block prefixes
-  if (kpp_small_table(n, dim, (int)T, k)) b += align256(sizeof(float) * n * n);  // distance table
-  if (kpp_small_table(n, dim, (int)T, k) || kpp_big_pairs(n, dim, (int)T, k))
-    b += 2 * (align256(sizeof(float) * T * T * n) + align256(sizeof(float) * T * T) +
-              align256(sizeof(int64_t) * T * T * T) + align256(sizeof(int64_t) * T * T));  // pair rounds
-  return b + 1024;
+  Carver cv(nullptr, 0);
+  KppBufs bf;
+  KppArgs a;
+  Kpp1Args b1;
+  kpp_carve(kpp_plan(n, dim, n_trials, k), cv, &bf, &a, &b1);
+  return cv.off + 1024;
+}
+
+// ---- pieces the launchers share ---------------------------------------------------------------------
+int kpp_transpose(const KppPlan& p, const float* X, float* XT, hipStream_t s) {
+  k_kpp_xt<<<dim3((unsigned)((p.n + kXtTile - 1) / kXtTile), (unsigned)((p.dim + kXtTile - 1) / kXtTile)), 256,
+             0, s>>>((int)p.n, p.dim, X, XT);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+int kpp_max_lds(const void* fn, size_t lds) {
+  GDD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return GDD_OK;
+}
+
+// the first centre: squared norms and its distances (k_kpp_init), then its potential and row
+int kpp_first_centre(const KppPlan& p, const KppArgs& a, const KppBufs& bf, int64_t first_id,
+                     hipStream_t s) {
+  if (p.lds > 65536)
+    for (const void* f : {(const void*)k_kpp_init, (const void*)k_kpp_round<true>, (const void*)k_kpp_round<false>})
+      if (const int rc = kpp_max_lds(f, p.lds)) return rc;
+  if (p.xt_before_init)
+    if (const int rc = kpp_transpose(p, a.X, bf.XT, s)) return rc;
+  const SklPlan p1{p.n, p.B1, 1, p.dim, 0, 0};
+  k_kpp_init<<<(unsigned)p.nblk, kThr, p.lds, s>>>(a, p1, first_id, bf.xsq, bf.closest0, bf.fsum0);
+  GDD_LAUNCHED();
+  if (a.w == nullptr && p.n >= (int64_t)kFirstSteps * 64 * 2) {  // large n, unit weights: staged chains
+    const size_t fl = sizeof(float) * 2 * kFirstSteps * 64;
+    if (const int rc = kpp_max_lds((const void*)k_kpp_first_big, fl)) return rc;
+    k_kpp_first_big<<<1, 1024, fl, s>>>(p.n, p.dim, a.X, bf.closest0, first_id, bf.st, a.centers, a.indices);
+  } else {
+    k_kpp_first<<<1, 64, 0, s>>>(p.n, p.dim, a.X, a.w, bf.closest0, first_id, bf.st, a.centers, a.indices);
+  }
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+// the one-workgroup-per-trial rounds' arguments; b1 arrives zeroed (padding too: it is part of the
+// pair chain's replay key) with its workspace pointers carved
+void kpp1_fill(Kpp1Args& b1, const KppPlan& p, const KppArgs& a, const float* XT) {
+  b1.n = p.n;
+  b1.m1 = a.m1;
+  b1.dim = p.dim;
+  b1.T = p.T;
+  b1.k = p.k;
+  b1.X = a.X;
+  b1.XT = XT;
+  b1.w = a.w;
+  b1.xsq = a.xsq;
+  b1.closest0 = a.closest0;
+  b1.st = a.st;
+  b1.uniforms = a.uniforms;
+  for (int q = 0; q < 2; ++q) b1.dist[q] = a.dist[q];
+  b1.centers = a.centers;
+  b1.indices = a.indices;
+  b1.plan = a.plan;
+  b1.exact = a.exact;
+}
+
+// rounds 1 .. k-2 recorded indices only (round 0's and k-1's rows are written)
+int kpp_gather(int k, int dim, const float* X, const int64_t* indices, float* centers, hipStream_t s) {
+  k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, s>>>(k, dim, X, indices, centers);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+int kpp1_finish(const Kpp1Args& b1, hipStream_t s) {
+  k_kpp1_final<<<1, 64, 0, s>>>(b1, b1.k - 1);
+  GDD_LAUNCHED();
+  return b1.k > 2 ? kpp_gather(b1.k, b1.dim, b1.X, b1.indices, b1.centers, s) : GDD_OK;
+}
+
+int kpp_finish(const KppPlan& p, const KppArgs& a, hipStream_t s) {
+  k_kpp_final<<<1, kThr, 0, s>>>(a, p.k - 1);
+  GDD_LAUNCHED();
+  return kpp_gather(p.k, p.dim, a.X, a.indices, a.centers, s);
+}
+
+// two rounds per launch, a trailing odd round alone: round(grid, c, lq, pair) launches one of them
+template <class Round>
+int kpp1_pair_rounds(const Kpp1Args& b1, hipStream_t s, Round round) {
+  int lq = 1, pair = 0;
+  for (int c = 1; c < b1.k; c += 2) {
+    lq = ((c - 1) / 2 + 1) & 1;
+    pair = c + 1 < b1.k ? 1 : 0;
+    round((unsigned)(pair ? b1.T * b1.T : b1.T), c, lq, pair);
+    GDD_LAUNCHED();
+  }
+  k_kpp1_final2<<<1, 64, 0, s>>>(b1, b1.k - 1, lq, pair);
+  GDD_LAUNCHED();
+  return b1.k > 2 ? kpp_gather(b1.k, b1.dim, b1.X, b1.indices, b1.centers, s) : GDD_OK;
+}
+
+// ---- the single-block paths (n <= 4096, T >= 2): one workgroup folds a whole trial ---------------------
+int kpp_single_begin(const KppPlan& p, const KppArgs& a, const KppBufs& bf, Kpp1Args& b1, hipStream_t s) {
+  kpp1_fill(b1, p, a, bf.XT);
+  if (p.xt_after_first)
+    if (const int rc = kpp_transpose(p, a.X, bf.XT, s)) return rc;
+  if (p.lds1 > 65536)
+    for (const void* f : {(const void*)k_kpp1_dist<true>, (const void*)k_kpp1_dist<false>})
+      if (const int rc = kpp_max_lds(f, p.lds1)) return rc;
+  k_kpp1_pick<<<1, kThr, 0, s>>>(b1, 0);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+// The chain's arguments are fixed by (b1, Dm, k): it is replayed as one recorded graph
+// (replay_or_run) — every launch then starts ~1 us sooner after the previous one
+int kpp_single_table_pair(const KppPlan& p, const KppBufs& bf, const Kpp1Args& b1, hipStream_t s) {
+  if (const int rc = launch_kpp_dmat(p.n, p.dim, b1.X, bf.XT, bf.xsq, bf.Dm, s)) return rc;
+  const float* Dm = bf.Dm;
+  const int overlap = p.overlap;
+  auto chain = [&](hipStream_t cs) -> int {
+    return kpp1_pair_rounds(b1, cs, [&](unsigned grid, int c, int lq, int pair) {
+      k_kpp1_dm2<<<grid, 256, 0, cs>>>(b1, Dm, c, lq, pair, overlap);
+    });
+  };
+  struct {
+    Kpp1Args b1;
+    const float* Dm;
+    int k, overlap;
+  } key;
+  std::memset(&key, 0, sizeof(key));
+  key.b1 = b1;
+  key.Dm = Dm;
+  key.k = p.k;
+  key.overlap = overlap;
+  return replay_or_run("kpp_pair_chain", &key, sizeof(key), s, chain);
+}
+
+int kpp_single_table(const KppPlan& p, const KppBufs& bf, const Kpp1Args& b1, hipStream_t s) {
+  if (const int rc = launch_kpp_dmat(p.n, p.dim, b1.X, bf.XT, bf.xsq, bf.Dm, s)) return rc;
+  for (int c = 1; c < p.k; ++c) {
+    k_kpp1_dm<<<(unsigned)p.T, 256, 0, s>>>(b1, bf.Dm, c);
+    GDD_LAUNCHED();
+  }
+  return kpp1_finish(b1, s);
+}
+
+// one launch per round: distances, then each trial's last workgroup folds it (no fences)
+int kpp_single_fused(const KppPlan& p, const Kpp1Args& b1, hipStream_t s) {
+  const dim3 gf((unsigned)((p.n + kFPts - 1) / kFPts), (unsigned)p.T);
+  GDD_HIP(hipMemsetAsync(b1.counter, 0, sizeof(unsigned) * (size_t)p.k * p.T, s));
+  for (int c = 1; c < p.k; ++c) {
+    if (p.seq)
+      k_kpp1_fused<true><<<gf, 256, 0, s>>>(b1, c);
+    else
+      k_kpp1_fused<false><<<gf, 256, 0, s>>>(b1, c);
+    GDD_LAUNCHED();
+  }
+  return kpp1_finish(b1, s);
+}
+
+// rows wider than kMaxDimF or more than 256 distance workgroups. Every round's pick writes its row:
+// no gather
+int kpp_single_two_launch(const KppPlan& p, const Kpp1Args& b1, hipStream_t s) {
+  const dim3 g1((unsigned)((p.n + kPts - 1) / kPts), (unsigned)(((p.T + kTg - 1) / kTg + 3) / 4));
+  for (int c = 1; c < p.k; ++c) {
+    if (p.seq)
+      k_kpp1_dist<true><<<g1, 256, p.lds1, s>>>(b1, c);
+    else
+      k_kpp1_dist<false><<<g1, 256, p.lds1, s>>>(b1, c);
+    GDD_LAUNCHED();
+    k_kpp1_pick<<<p.T, kThr, 0, s>>>(b1, c);
+    GDD_LAUNCHED();
+  }
+  k_kpp1_final<<<1, 64, 0, s>>>(b1, p.k - 1);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+// ---- the multi-block paths -------------------------------------------------------------------------
+int kpp_split(const KppPlan& p, const KppArgs& a, hipStream_t s) {
+  void (*dists)(KppArgs, int) = nullptr;
+  switch (p.T) {
+    case 2: dists = k_kpp_dists<2>; break;
+    case 3: dists = k_kpp_dists<3>; break;
+    case 4: dists = k_kpp_dists<4>; break;
+    case 5: dists = k_kpp_dists<5>; break;
+    case 6: dists = k_kpp_dists<6>; break;
+    case 7: dists = k_kpp_dists<7>; break;
+    default: dists = k_kpp_dists<8>; break;
+  }
+  if (const int rc = kpp_max_lds((const void*)dists, p.lds_split)) return rc;
+  for (int c = 1; c < p.k; ++c) {
+    k_kpp_round<true, true><<<dim3(1, p.T), kThr, p.lds, s>>>(a, c);  // fold, winner, candidates
+    GDD_LAUNCHED();
+    dists<<<(unsigned)p.nblk, kThr, p.lds_split, s>>>(a, c);          // every trial's distances
+    GDD_LAUNCHED();
+  }
+  return kpp_finish(p, a, s);
+}
+
+// the distances once per fit (~n^2 dim fp64 fmas), then one 1024-thread workgroup per trial reads
+// its rows from the table; one launch on a grid of 1 gives round 1's candidates from the first centre
+typedef void (*KppBigFn)(Kpp1Args, const float*, int);
+int kpp_big_begin(const KppPlan& p, const KppArgs& a, const KppBufs& bf, Kpp1Args& b1, KppBigFn* big,
+                  hipStream_t s) {
+  if (const int rc = launch_kpp_dmat(p.n, p.dim, a.X, bf.XT, bf.xsq, bf.Dbig, s)) return rc;
+  kpp1_fill(b1, p, a, nullptr);
+  KppBigFn f = k_kpp1_big<8>;
+  if (p.ept == 16) f = k_kpp1_big<16>;
+  if (p.ept == 32) f = k_kpp1_big<32>;
+  if (const int rc = kpp_max_lds((const void*)f, p.lds_big)) return rc;
+  f<<<1, kBigThr, p.lds_big, s>>>(b1, bf.Dbig, 0);
+  GDD_LAUNCHED();
+  *big = f;
+  return GDD_OK;
+}
+
+int kpp_big_pair(const KppPlan& p, const KppArgs& a, const KppBufs& bf, Kpp1Args& b1, hipStream_t s) {
+  KppBigFn big;
+  if (const int rc = kpp_big_begin(p, a, bf, b1, &big, s)) return rc;
+  void (*big2)(Kpp1Args, const float*, int, int, int) = k_kpp1_big2<8>;  // n <= 8192: ept == 8
+  if (const int rc = kpp_max_lds((const void*)big2, p.lds_big)) return rc;
+  return kpp1_pair_rounds(b1, s, [&](unsigned grid, int c, int lq, int pair) {
+    big2<<<grid, kBigThr, p.lds_big, s>>>(b1, bf.Dbig, c, lq, pair);
+  });
+}
+
+int kpp_big(const KppPlan& p, const KppArgs& a, const KppBufs& bf, Kpp1Args& b1, hipStream_t s) {
+  KppBigFn big;
+  if (const int rc = kpp_big_begin(p, a, bf, b1, &big, s)) return rc;
+  for (int c = 1; c < p.k; ++c) {
+    big<<<(unsigned)p.T, kBigThr, p.lds_big, s>>>(b1, bf.Dbig, c);
+    GDD_LAUNCHED();
+  }
+  return kpp1_finish(b1, s);
+}
+
+// one workgroup per (block, trial); with a.D set the distances come from the table
+int kpp_block(const KppPlan& p, const KppArgs& a, hipStream_t s) {
+  for (int c = 1; c < p.k; ++c) {
+    if (p.seq)
+      k_kpp_round<true><<<dim3((unsigned)p.nblk, p.T), kThr, p.lds, s>>>(a, c);
+    else
+      k_kpp_round<false><<<dim3((unsigned)p.nblk, p.T), kThr, p.lds, s>>>(a, c);
+    GDD_LAUNCHED();
+    if (p.T == 1) {
+      k_kpp_pot1<<<1, 64, 0, s>>>(p.n, a.dist[c & 1], a.w, a.pot1 + (c & 1));
+      GDD_LAUNCHED();
+    }
+  }
+  return kpp_finish(p, a, s);
+}
+
+int kpp_block_table(const KppPlan& p, KppArgs& a, const KppBufs& bf, hipStream_t s) {
+  if (const int rc = launch_kpp_dmat(p.n, p.dim, a.X, bf.XT, bf.xsq, bf.Dbig, s)) return rc;
+  a.D = bf.Dbig;
+  return kpp_block(p, a, s);
+}
+
+// what gdd_kmeans_plusplus refuses, for the path query
+bool kpp_shape_ok(int64_t n, int dim, int n_trials, int k) {
+  return n > 0 && dim > 0 && k > 0 && k <= n && n_trials >= 1 && n_trials <= kMaxTrials && dim <= 4096 &&
+         n < (int64_t)INT_MAX * kBlk;
+}
+
+}  // namespace
+
+// k (centres) sizes the fused rounds' arrival counters and gates the tables. This query bounds it
+// by n (an upper bound for every k); gdd_kmeans_plusplus_ws_bytes_k sizes for the caller's k
+extern "C" size_t gdd_kmeans_plusplus_ws_bytes(int64_t n, int dim, int n_trials) {
+  return kpp_ws_bytes(n, dim, n_trials, (int)std::min<int64_t>(n, INT_MAX));
+}
+
+extern "C" size_t gdd_kmeans_plusplus_ws_bytes_k(int64_t n, int dim, int n_trials, int k) {
+  return kpp_ws_bytes(n, dim, n_trials, k);
+}
+
+extern "C" const char* gdd_kmeans_plusplus_path(int64_t n, int dim, int n_trials, int k) {
+  return kpp_shape_ok(n, dim, n_trials, k) ? kpp_path_name(kpp_plan(n, dim, n_trials, k)) : "invalid";
 }
 
 extern "C" int gdd_kmeans_plusplus(int64_t n, int dim, const float* X, const float* w, int k,
@@ -3524,325 +3910,50 @@ extern "C" int gdd_kmeans_plusplus(int64_t n, int dim, const float* X, const flo
   GDD_REQUIRE(first_id >= 0 && first_id < n, "kmeans++: first_id out of range");
   GDD_REQUIRE(X && centers && indices && ws && (k == 1 || uniforms), "kmeans++: null pointer");
   hipStream_t s = to_hip(stream);
-  const int T = n_trials;
-  const int nblk = (int)((n + kBlk - 1) / kBlk);
+  const KppPlan p = kpp_plan(n, dim, n_trials, k);
   Carver cv(ws, ws_bytes);
+  KppBufs bf;
   KppArgs a{};
-  KppState* st = cv.take<KppState>(1);
-  double* xsq = cv.take<double>(n);
-  float* closest0 = cv.take<float>(n);
-  double* fsum0 = cv.take<double>(nblk);
-  for (int q = 0; q < 2; ++q) a.dist[q] = cv.take<float>(n * (size_t)T);
-  for (int q = 0; q < 2; ++q) a.vblk[q] = cv.take<float>((size_t)nblk * T);
-  for (int q = 0; q < 2; ++q) a.fsum[q] = cv.take<double>((size_t)nblk * T);
-  for (int q = 0; q < 2; ++q) a.cand[q] = cv.take<int64_t>(kMaxTrials);
-  a.pot1 = cv.take<float>(2);
-  a.winq = cv.take<int>(2);
   Kpp1Args b1;
   std::memset(&b1, 0, sizeof(b1));  // padding too: b1 is part of the chain's replay key
-  for (int q = 0; q < 2; ++q) b1.potv[q] = cv.take<float>(T);
-  for (int q = 0; q < 2; ++q) b1.candw[q] = cv.take<int64_t>((size_t)T * T);
-  for (int q = 0; q < 2; ++q) b1.candself[q] = cv.take<int64_t>(T);
-  for (int q = 0; q < 2; ++q) b1.candr[q] = cv.take<int64_t>(T);
-  for (int q = 0; q < 2; ++q) b1.candn[q] = cv.take<double>(T);
-  b1.win = cv.take<int>(2);
-  b1.counter = cv.take<unsigned>((size_t)std::max(k, 1) * T);  // rounds c < k, trial t
-  float* XT = (n <= kBlk || n * (int64_t)dim < INT_MAX) ? cv.take<float>((size_t)n * dim) : nullptr;
-  float* Dbig = kpp_big_table(n, dim, T, k) ? cv.take<float>((size_t)n * n) : nullptr;
-  // the per-block table rounds keep each round's block prefixes for the next round's count (r05)
-  const bool big1 = n <= kpp_big1_max() && T >= 2 && !forced("kpp_no_big1");
-  for (int q = 0; q < 2; ++q) a.pfx[q] = (Dbig && !big1) ? cv.take<double>((size_t)n * T) : nullptr;
-  float* Dm = kpp_small_table(n, dim, T, k) ? cv.take<float>((size_t)n * n) : nullptr;
-  const bool pairs_big = Dbig && big1 && kpp_big_pairs(n, dim, T, k);
-  if (Dm || pairs_big) {
-    for (int q = 0; q < 2; ++q) {
-      b1.dist2[q] = cv.take<float>((size_t)T * T * n);
-      b1.potv2[q] = cv.take<float>((size_t)T * T);
-      b1.candw2[q] = cv.take<int64_t>((size_t)T * T * T);
-      b1.candself2[q] = cv.take<int64_t>((size_t)T * T);
-    }
-  }
+  kpp_carve(p, cv, &bf, &a, &b1);
   if (!cv.ok()) return fail(GDD_E_WORKSPACE, "kmeans++: workspace too small");
   a.n = n;
   a.m1 = n & ~3ll;
   a.dim = dim;
-  a.T = T;
-  a.nblk = nblk;
+  a.T = p.T;
+  a.nblk = (int)p.nblk;
   a.nsg = (int)((a.m1 + kBlk - 1) / kBlk);
   a.X = X;
-  a.XT = n > kBlk ? XT : nullptr;  // the single-block path keeps its own copy in b1
+  a.XT = p.xt_before_init ? bf.XT : nullptr;  // the single-block paths keep their copy in b1
   a.w = w;
-  a.xsq = xsq;
-  a.closest0 = closest0;
-  a.fsum0 = fsum0;
+  a.xsq = bf.xsq;
+  a.closest0 = bf.closest0;
+  a.fsum0 = bf.fsum0;
   a.uniforms = uniforms;
-  a.st = st;
+  a.st = bf.st;
   a.centers = centers;
   a.indices = indices;
-  a.plan = SklPlan{n, skl_batch_size(T, n, dim), T, dim, 0, 0};
-  a.plan.all_seq = skl_all_seq(n, T, dim, a.plan.B) ? 1 : 0;
-  {  // cum_tol's mode (diagnostic): GDD_KPP_EXACT=0 never replays (tests only), 2 always replays
-    const char* ex = getenv("GDD_KPP_EXACT");
-    a.exact = ex ? atoi(ex) : 1;
-  }
-  const SklPlan p1{n, skl_batch_size(1, n, dim), 1, dim, 0, 0};
-  const size_t lds = sizeof(double) * (size_t)dim + sizeof(float) * (kBlk + kChainPad);  // + chain read-ahead
-  const bool seq = a.plan.all_seq != 0;
-  const bool single = nblk == 1 && T >= 2 && (!seq || XT);
-  if (lds > 65536) {
-    const void* fns[] = {(const void*)k_kpp_init, (const void*)k_kpp_round<true>,
-                         (const void*)k_kpp_round<false>};
-    for (const void* f : fns)
-      GDD_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  if (a.XT) {
-    k_kpp_xt<<<dim3((unsigned)((n + kXtTile - 1) / kXtTile), (unsigned)((dim + kXtTile - 1) / kXtTile)), 256, 0,
-               s>>>((int)n, dim, X, XT);
-    GDD_LAUNCHED();
-  }
-  k_kpp_init<<<nblk, kThr, lds, s>>>(a, p1, first_id, xsq, closest0, fsum0);
-  GDD_LAUNCHED();
-  if (w == nullptr && n >= (int64_t)kFirstSteps * 64 * 2) {  // large n, unit weights: staged chains
-    const size_t fl = sizeof(float) * 2 * kFirstSteps * 64;
-    GDD_HIP(hipFuncSetAttribute((const void*)k_kpp_first_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl));
-    k_kpp_first_big<<<1, 1024, fl, s>>>(n, dim, X, closest0, first_id, st, centers, indices);
-  } else {
-    k_kpp_first<<<1, 64, 0, s>>>(n, dim, X, w, closest0, first_id, st, centers, indices);
-  }
-  GDD_LAUNCHED();
-  if (k == 1) return GDD_OK;
-  if (single) {
-    b1.n = n;
-    b1.m1 = a.m1;
-    b1.dim = dim;
-    b1.T = T;
-    b1.k = k;
-    b1.X = X;
-    b1.XT = XT;
-    b1.w = w;
-    b1.xsq = xsq;
-    b1.closest0 = closest0;
-    b1.st = st;
-    b1.uniforms = uniforms;
-    for (int q = 0; q < 2; ++q) b1.dist[q] = a.dist[q];
-    b1.centers = centers;
-    b1.indices = indices;
-    b1.plan = a.plan;
-    b1.exact = a.exact;
-    if (seq) {
-      k_kpp_xt<<<dim3((unsigned)((n + kXtTile - 1) / kXtTile), (unsigned)((dim + kXtTile - 1) / kXtTile)), 256, 0,
-               s>>>((int)n, dim, X, XT);
-      GDD_LAUNCHED();
+  a.plan = SklPlan{n, p.B, p.T, dim, p.seq ? 1 : 0, 0};
+  a.exact = p.exact;
+  if (const int rc = kpp_first_centre(p, a, bf, first_id, s)) return rc;
+  switch (p.path) {
+    case KPP_FIRST_ONLY: return GDD_OK;
+    case KPP_SINGLE_TABLE_PAIR:
+    case KPP_SINGLE_TABLE:
+    case KPP_SINGLE_FUSED:
+    case KPP_SINGLE_TWO_LAUNCH: {
+      if (const int rc = kpp_single_begin(p, a, bf, b1, s)) return rc;
+      if (p.path == KPP_SINGLE_TABLE_PAIR) return kpp_single_table_pair(p, bf, b1, s);
+      if (p.path == KPP_SINGLE_TABLE) return kpp_single_table(p, bf, b1, s);
+      if (p.path == KPP_SINGLE_FUSED) return kpp_single_fused(p, b1, s);
+      return kpp_single_two_launch(p, b1, s);
     }
-    const size_t lds1 = sizeof(double) * (size_t)T * std::max(dim, 48);
-    if (lds1 > 65536)
-      for (const void* f : {(const void*)k_kpp1_dist<true>, (const void*)k_kpp1_dist<false>})
-        GDD_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    const dim3 g1((unsigned)((n + kPts - 1) / kPts), (unsigned)(((T + kTg - 1) / kTg + 3) / 4));
-    k_kpp1_pick<<<1, kThr, 0, s>>>(b1, 0);
-    GDD_LAUNCHED();
-    // the distance table pays once the rounds it saves (~3 us each) cover its one-off build
-    if (seq && Dm && k >= kDmMinK && !forced("kpp_no_table")) {
-      if (const int rc = launch_kpp_dmat(n, dim, X, XT, xsq, Dm, s)) return rc;
-      if (T <= kPairMaxT && !forced("kpp_single_round")) {
-        // two rounds per launch (a trailing odd round alone). The chain's arguments are fixed by
-        // (b1, Dm, k): it is replayed as one recorded graph (replay_or_run) — every launch then
-        // starts ~1 us sooner after the previous one
-        // the pair's two folds overlapped (kpp1_fold_pair); GDD_FORCE=kpp_pair_serial: one after the other
-        const int overlap = forced("kpp_pair_serial") ? 0 : 1;
-        auto chain = [&](hipStream_t cs) -> int {
-          int lq = 1, pair = 0;
-          for (int c = 1; c < k; c += 2) {
-            lq = ((c - 1) / 2 + 1) & 1;
-            pair = c + 1 < k ? 1 : 0;
-            const unsigned grid = (unsigned)(pair ? T * T : T);
-            k_kpp1_dm2<<<grid, 256, 0, cs>>>(b1, Dm, c, lq, pair, overlap);
-            GDD_LAUNCHED();
-          }
-          k_kpp1_final2<<<1, 64, 0, cs>>>(b1, k - 1, lq, pair);
-          GDD_LAUNCHED();
-          if (k > 2) {
-            k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, cs>>>(
-                k, dim, X, indices, centers);
-            GDD_LAUNCHED();
-          }
-          return GDD_OK;
-        };
-        struct {
-          Kpp1Args b1;
-          const float* Dm;
-          int k, overlap;
-        } key;
-        std::memset(&key, 0, sizeof(key));
-        key.b1 = b1;
-        key.Dm = Dm;
-        key.k = k;
-        key.overlap = overlap;
-        return replay_or_run("kpp_pair_chain", &key, sizeof(key), s, chain);
-      }
-      for (int c = 1; c < k; ++c) {
-        k_kpp1_dm<<<(unsigned)T, 256, 0, s>>>(b1, Dm, c);
-        GDD_LAUNCHED();
-      }
-      k_kpp1_final<<<1, 64, 0, s>>>(b1, k - 1);
-      GDD_LAUNCHED();
-      if (k > 2) {
-        k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, s>>>(k, dim, X, indices,
-                                                                                         centers);
-        GDD_LAUNCHED();
-      }
-      return GDD_OK;
-    }
-    const dim3 gf((unsigned)((n + kFPts - 1) / kFPts), (unsigned)T);
-    if (dim <= kMaxDimF && gf.x * gf.y <= 256 && !forced("kpp_two_launch")) {
-      // one launch per round: distances, then each trial's last workgroup folds it (no fences)
-      GDD_HIP(hipMemsetAsync(b1.counter, 0, sizeof(unsigned) * (size_t)k * T, s));
-      for (int c = 1; c < k; ++c) {
-        if (seq)
-          k_kpp1_fused<true><<<gf, 256, 0, s>>>(b1, c);
-        else
-          k_kpp1_fused<false><<<gf, 256, 0, s>>>(b1, c);
-        GDD_LAUNCHED();
-      }
-      k_kpp1_final<<<1, 64, 0, s>>>(b1, k - 1);
-      GDD_LAUNCHED();
-      if (k > 2) {  // rounds 1..k-2 recorded indices only (round 0's and k-1's rows are written)
-        k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, s>>>(k, dim, X, indices,
-                                                                                         centers);
-        GDD_LAUNCHED();
-      }
-      return GDD_OK;
-    }
-    for (int c = 1; c < k; ++c) {
-      if (seq)
-        k_kpp1_dist<true><<<g1, 256, lds1, s>>>(b1, c);
-      else
-        k_kpp1_dist<false><<<g1, 256, lds1, s>>>(b1, c);
-      GDD_LAUNCHED();
-      k_kpp1_pick<<<T, kThr, 0, s>>>(b1, c);
-      GDD_LAUNCHED();
-    }
-    k_kpp1_final<<<1, 64, 0, s>>>(b1, k - 1);
-    GDD_LAUNCHED();
-    return GDD_OK;
+    case KPP_SPLIT: return kpp_split(p, a, s);
+    case KPP_BIG_PAIR: return kpp_big_pair(p, a, bf, b1, s);
+    case KPP_BIG: return kpp_big(p, a, bf, b1, s);
+    case KPP_BLOCK_TABLE: return kpp_block_table(p, a, bf, s);
+    case KPP_BLOCK: return kpp_block(p, a, s);
   }
-  const size_t lds_split = sizeof(double) * (size_t)T * dim + sizeof(float) * (size_t)T * kBlk;
-  // the split path has one workgroup per 4096-point block: it pays only when there are enough
-  // blocks to fill the chip (products' 2.45M points: 598 blocks). With few blocks the per-(block,
-  // trial) rounds win (6,040 points: 22 vs 69 us per round; 40,000: 47 vs 84).
-  const bool split = seq && a.XT && T >= 2 && T <= kSplitMaxT && lds_split <= 150 * 1024 &&
-                     nblk >= kSplitMinBlocks && !forced("kpp_no_split");
-  if (split) {
-    void (*dists)(KppArgs, int) = nullptr;
-    switch (T) {
-      case 2: dists = k_kpp_dists<2>; break;
-      case 3: dists = k_kpp_dists<3>; break;
-      case 4: dists = k_kpp_dists<4>; break;
-      case 5: dists = k_kpp_dists<5>; break;
-      case 6: dists = k_kpp_dists<6>; break;
-      case 7: dists = k_kpp_dists<7>; break;
-      default: dists = k_kpp_dists<8>; break;
-    }
-    GDD_HIP(hipFuncSetAttribute((const void*)dists, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_split));
-    for (int c = 1; c < k; ++c) {
-      k_kpp_round<true, true><<<dim3(1, T), kThr, lds, s>>>(a, c);   // fold, winner, candidates
-      GDD_LAUNCHED();
-      dists<<<nblk, kThr, lds_split, s>>>(a, c);                    // every trial's distances
-      GDD_LAUNCHED();
-    }
-    k_kpp_final<<<1, kThr, 0, s>>>(a, k - 1);
-    GDD_LAUNCHED();
-    k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, s>>>(k, dim, X, indices,
-                                                                                     centers);
-    GDD_LAUNCHED();
-    return GDD_OK;
-  }
-  if (Dbig && seq && a.XT) {  // the distances once per fit (~n^2 dim fp64 fmas), then table rounds
-    if (const int rc = launch_kpp_dmat(n, dim, X, a.XT, xsq, Dbig, s)) return rc;
-    a.D = Dbig;
-    if (big1) {
-      // one 1024-thread workgroup per trial (k_kpp1_big); GDD_FORCE=kpp_no_big1 keeps the per-block rounds
-      b1.n = n;
-      b1.m1 = a.m1;
-      b1.dim = dim;
-      b1.T = T;
-      b1.k = k;
-      b1.X = X;
-      b1.w = w;
-      b1.xsq = xsq;
-      b1.closest0 = closest0;
-      b1.st = st;
-      b1.uniforms = uniforms;
-      for (int q = 0; q < 2; ++q) b1.dist[q] = a.dist[q];
-      b1.centers = centers;
-      b1.indices = indices;
-      b1.plan = a.plan;
-      b1.exact = a.exact;
-      void (*big)(Kpp1Args, const float*, int) = nullptr;
-      int ept = 0;
-      if (n <= (int64_t)kBigThr * 8) {
-        big = k_kpp1_big<8>;
-        ept = 8;
-      } else if (n <= (int64_t)kBigThr * 16) {
-        big = k_kpp1_big<16>;
-        ept = 16;
-      } else {
-        big = k_kpp1_big<32>;
-        ept = 32;
-      }
-      const size_t lds_big = sizeof(float) * ((size_t)kBigThr * ept + kChainPad);
-      GDD_HIP(hipFuncSetAttribute((const void*)big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-      big<<<1, kBigThr, lds_big, s>>>(b1, Dbig, 0);  // round 1's candidates from the first centre
-      GDD_LAUNCHED();
-      if (pairs_big && !forced("kpp_single_round")) {  // two rounds per launch (r06)
-        void (*big2)(Kpp1Args, const float*, int, int, int) = k_kpp1_big2<8>;  // n <= 8192: ept == 8
-        GDD_HIP(hipFuncSetAttribute((const void*)big2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-        int lq = 1, pair = 0;
-        for (int c = 1; c < k; c += 2) {
-          lq = ((c - 1) / 2 + 1) & 1;
-          pair = c + 1 < k ? 1 : 0;
-          big2<<<(unsigned)(pair ? T * T : T), kBigThr, lds_big, s>>>(b1, Dbig, c, lq, pair);
-          GDD_LAUNCHED();
-        }
-        k_kpp1_final2<<<1, 64, 0, s>>>(b1, k - 1, lq, pair);
-        GDD_LAUNCHED();
-        if (k > 2) {
-          k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, s>>>(k, dim, X, indices,
-                                                                                           centers);
-          GDD_LAUNCHED();
-        }
-        return GDD_OK;
-      }
-      for (int c = 1; c < k; ++c) {
-        big<<<(unsigned)T, kBigThr, lds_big, s>>>(b1, Dbig, c);
-        GDD_LAUNCHED();
-      }
-      k_kpp1_final<<<1, 64, 0, s>>>(b1, k - 1);
-      GDD_LAUNCHED();
-      if (k > 2) {
-        k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, s>>>(k, dim, X, indices,
-                                                                                         centers);
-        GDD_LAUNCHED();
-      }
-      return GDD_OK;
-    }
-  }
-  for (int c = 1; c < k; ++c) {
-    if (seq)
-      k_kpp_round<true><<<dim3(nblk, T), kThr, lds, s>>>(a, c);
-    else
-      k_kpp_round<false><<<dim3(nblk, T), kThr, lds, s>>>(a, c);
-    GDD_LAUNCHED();
-    if (T == 1) {
-      k_kpp_pot1<<<1, 64, 0, s>>>(n, a.dist[c & 1], w, a.pot1 + (c & 1));
-      GDD_LAUNCHED();
-    }
-  }
-  k_kpp_final<<<1, kThr, 0, s>>>(a, k - 1);
-  GDD_LAUNCHED();
-  k_kpp_gather_centres<<<(unsigned)(((int64_t)k * dim + 255) / 256), 256, 0, s>>>(k, dim, X, indices,
-                                                                                   centers);
-  GDD_LAUNCHED();
   return GDD_OK;
 }

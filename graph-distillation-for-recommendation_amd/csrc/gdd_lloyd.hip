@@ -236,18 +236,42 @@ __global__ void k_offsets(int64_t n, const int32_t* __restrict__ skeys, int k,
   for (int c = prev + 1; c <= cur && c <= k; ++c) offsets[c] = (int32_t)i;
 }
 
-size_t group_ws(int64_t n, int k) {
+// group_dev's buffers beyond the one-launch form (which needs none)
+struct GroupWs {
+  int32_t *a, *b;  // counting: the histogram matrix and its scan; radix: the row ids and the sorted keys
+  size_t sb;       // the scan's / the sort's own workspace
+  void* sws;
+};
+
+// the counting form's buffers for a histogram matrix of `cells`
+void carve_count(Carver& cv, int64_t cells, GroupWs* g) {
+  g->a = cv.take<int32_t>(cells);
+  g->b = cv.take<int32_t>(cells);
+  g->sb = scan_i32_ws_bytes(cells);
+  g->sws = cv.take<char>(g->sb);
+}
+
+// carves them from ws (a null ws: measures) and returns the bytes they take
+size_t carve_group(void* ws, int64_t n, int k, GroupWs* g) {
+  Carver cv(ws, 0);
   if (k <= kCountMaxK) {
-    const GroupPlan p = group_plan(n, k);
-    const int64_t cells = (int64_t)k * p.ntiles;
-    return 2 * align256(sizeof(int32_t) * (size_t)cells) + align256(scan_i32_ws_bytes(cells)) + 256;
+    carve_count(cv, (int64_t)k * group_plan(n, k).ntiles, g);
+  } else {
+    g->a = cv.take<int32_t>(n);
+    g->b = cv.take<int32_t>(n);
+    g->sb = sort_pairs_ws_bytes(n);
+    g->sws = cv.take<char>(g->sb);
   }
-  return align256(sizeof(int32_t) * (size_t)n) * 2 + sort_pairs_ws_bytes(n) + 1024;
+  return cv.off;
+}
+
+size_t group_ws(int64_t n, int k) {
+  GroupWs g;
+  return carve_group(nullptr, n, k, &g) + (k <= kCountMaxK ? 256 : 1024);
 }
 
 int group_dev(int64_t n, const int32_t* labels, int k, int32_t* perm, int32_t* offsets, void* ws,
               size_t ws_bytes, const int32_t* stop, int step_i, hipStream_t s) {
-  Carver cv(ws, ws_bytes);
   if (n <= kGrpSmallMaxN && k <= kGrpSmallMaxK && !forced("group_split")) {
     int bits = 1;
     while ((1ll << bits) < (long long)k) ++bits;
@@ -263,11 +287,11 @@ int group_dev(int64_t n, const int32_t* labels, int k, int32_t* perm, int32_t* o
     const GroupPlan p = group_plan(n, k);
     const int64_t cells = (int64_t)k * p.ntiles;
     GDD_REQUIRE(cells < INT_MAX, "group_by_label: k x tiles too large");
-    int32_t* ghist = cv.take<int32_t>(cells);
-    int32_t* gscan = cv.take<int32_t>(cells);
-    const size_t sb = scan_i32_ws_bytes(cells);
-    void* sws = cv.take<char>(sb);
-    if (!cv.ok()) return fail(GDD_E_WORKSPACE, "group_by_label: workspace too small");
+    GroupWs g;
+    if (carve_group(ws, n, k, &g) > ws_bytes) return fail(GDD_E_WORKSPACE, "group_by_label: workspace too small");
+    int32_t *ghist = g.a, *gscan = g.b;
+    const size_t sb = g.sb;
+    void* sws = g.sws;
     int bits = 1;
     while ((1ll << bits) < (long long)k) ++bits;
     const unsigned grid = (unsigned)((p.ntiles + p.waves - 1) / p.waves);
@@ -296,11 +320,11 @@ int group_dev(int64_t n, const int32_t* labels, int k, int32_t* perm, int32_t* o
   }
   // the radix path does not read the stop word: after a stop it regroups the (unchanged) labels
   // into the workspace, which nothing reads any more
-  int32_t* iota = cv.take<int32_t>(n);
-  int32_t* skeys = cv.take<int32_t>(n);
-  const size_t sb = sort_pairs_ws_bytes(n);
-  void* sws = cv.take<char>(sb);
-  if (!cv.ok()) return fail(GDD_E_WORKSPACE, "group_by_label: workspace too small");
+  GroupWs g;
+  if (carve_group(ws, n, k, &g) > ws_bytes) return fail(GDD_E_WORKSPACE, "group_by_label: workspace too small");
+  int32_t *iota = g.a, *skeys = g.b;
+  const size_t sb = g.sb;
+  void* sws = g.sws;
   int bits = 1;
   while ((1ll << bits) < (long long)k) ++bits;
   k_iota<<<blocks_of(n), 256, 0, s>>>(n, iota);
@@ -1333,13 +1357,6 @@ extern "C" int gdd_relocate_distances(int64_t n, int dim, const float* X, const 
 // ---- the device-resident Lloyd loop -----------------------------------------------------------------
 extern "C" size_t gdd_lloyd_state_bytes(void) { return sizeof(LloydState); }
 
-// the bounded E-step's buffers: ||x|| (fp64), the two bounds (fp64), the failing-row list, second
-// distances, a counter, the centre separations and two global bounds
-static size_t prune_ws(int64_t n, int k) {
-  return 4 * align256(sizeof(double) * (size_t)n) + align256(sizeof(float) * (size_t)n) +
-         align256(sizeof(double) * (size_t)k) + 3 * 256;
-}
-
 // The M-step's zero-padded copy of X (r05): for dim % 4 != 0 the fold gathers its rows one float at a
 // time (a 188-byte row is 16-byte aligned one time in four, and unaligned 16-byte loads measured
 // slower, §4); a copy with rows of round4(dim) floats, made once per run, lets it gather 16-byte
@@ -1347,11 +1364,6 @@ static size_t prune_ws(int64_t n, int k) {
 // sums are the same bits.
 static int fold_pad_dim(int64_t n, int dim) {
   return (dim % 4 != 0 && n >= kFoldPadMinRows) ? (dim + 3) & ~3 : 0;
-}
-
-static size_t fold_pad_ws(int64_t n, int dim) {
-  const int dp = fold_pad_dim(n, dim);
-  return dp ? align256(sizeof(float) * (size_t)n * (size_t)dp) + 256 : 0;
 }
 
 __global__ void k_pad_rows(int64_t n, int dim, int dp, const float* __restrict__ X, float* __restrict__ Xp) {
@@ -1384,9 +1396,14 @@ struct LloydWs {
   float* sec;
   double *sep, *glob;
   int64_t* count;
+  float* Xp;  // the fold's padded copy of X (nullptr: fold_pad_dim says none); gdd_kmeans_lloyd_run only
 };
 
-static bool carve_lloyd(void* ws, size_t ws_bytes, int64_t n, int dim, int k, LloydWs* w) {
+// Carves the loop's buffers from ws and says whether they fit in ws_bytes; a null ws only measures.
+// *bytes: what gdd_kmeans_lloyd_run needs — the buffers (the bounded E-step's, ~36 B per row, only
+// where it can run: ADVICE r3), 1024 bytes of slack and behind them the fold's padded copy
+static bool carve_lloyd(void* ws, size_t ws_bytes, int64_t n, int dim, int k, LloydWs* w,
+                        size_t* bytes = nullptr) {
   Carver cv(ws, ws_bytes);
   w->keys = cv.take<unsigned long long>(n);
   w->cn2 = cv.take<float>(k);
@@ -1404,14 +1421,22 @@ static bool carve_lloyd(void* ws, size_t ws_bytes, int64_t n, int dim, int k, Ll
   w->sep = cv.take<double>(pk);
   w->glob = cv.take<double>(2);
   w->count = cv.take<int64_t>(1);
-  return cv.ok();
+  const bool fits = cv.ok();
+  // the copy starts at the first 256-byte address past the slack, whatever ws's own alignment:
+  // up to 255 bytes more than its rows
+  const int dp = fold_pad_dim(n, dim);
+  const size_t pad_at = cv.off + 1024;
+  w->Xp = dp && ws ? reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + pad_at + 255) & ~uintptr_t(255))
+                   : nullptr;
+  if (bytes) *bytes = pad_at + (dp ? align256(sizeof(float) * (size_t)n * (size_t)dp) + 256 : 0);
+  return fits;
 }
 
 extern "C" size_t gdd_kmeans_lloyd_ws_bytes(int64_t n, int dim, int k) {
-  // the bounded E-step's buffers (~36 B per row) only where it can run
-  return align256(sizeof(unsigned long long) * (size_t)n) + align256(sizeof(float) * (size_t)k) +
-         align256(sizeof(int32_t) * (size_t)n) + align256(sizeof(int32_t) * (size_t)(k + 1)) +
-         group_ws(n, k) + (lloyd_prune_ok(dim, k) ? prune_ws(n, k) : 3 * 256) + 1024 + fold_pad_ws(n, dim);
+  LloydWs w;
+  size_t bytes = 0;
+  carve_lloyd(nullptr, 0, n, dim, k, &w, &bytes);
+  return bytes;
 }
 
 extern "C" size_t gdd_kmeans_lloyd_host_ws_bytes(void) { return 4 * sizeof(LloydState); }
@@ -1467,10 +1492,8 @@ extern "C" int gdd_kmeans_lloyd_run(int64_t n, int dim, const float* X, int k, f
   int dpad = 0;
   {  // the fold's zero-padded copy of X at the end of the workspace (fold_no_pad: gather X itself)
     const int dp = fold_pad_dim(n, dim);
-    const size_t base = gdd_kmeans_lloyd_ws_bytes(n, dim, k) - fold_pad_ws(n, dim);
-    const uintptr_t at = (reinterpret_cast<uintptr_t>(ws) + base + 255) & ~uintptr_t(255);
-    if (dp && !forced("fold_no_pad") && ws_bytes >= base + fold_pad_ws(n, dim)) {
-      float* Xp = reinterpret_cast<float*>(at);
+    if (lw.Xp && !forced("fold_no_pad")) {
+      float* Xp = lw.Xp;
       const int64_t total = n * (dp / 4);
       k_pad_rows<<<(unsigned)std::min<int64_t>((total + 255) / 256, 8192), 256, 0, s>>>(n, dim, dp, X, Xp);
       GDD_LAUNCHED();
@@ -1935,9 +1958,26 @@ __global__ __launch_bounds__(256) void k_reduce_check(int k, const long long* __
 // group_dev's workspace for any row count up to n (a rank groups its own rows; the tile plan, and
 // with it the histogram matrix, is not monotone in the row count)
 size_t reduce_group_ws(int64_t n, int k) {
-  const int64_t cells = (int64_t)k * ((n + kTileUnit - 1) / kTileUnit);
-  const size_t bound = 2 * align256(sizeof(int32_t) * (size_t)cells) + align256(scan_i32_ws_bytes(cells)) + 256;
-  return std::max(group_ws(n, k), bound);
+  Carver cv(nullptr, 0);
+  GroupWs g;
+  carve_count(cv, (int64_t)k * ((n + kTileUnit - 1) / kTileUnit), &g);  // the finest tiling's matrix
+  return std::max(group_ws(n, k), cv.off + 256);
+}
+
+// gdd_lloyd_reduce_local's buffers carved from ws (a null ws: measured); returns the workspace it needs
+struct ReduceWs {
+  int32_t* perm;
+  int32_t* offsets;
+  size_t gb;
+  void* gws;
+};
+size_t carve_reduce(void* ws, int64_t n, int k, ReduceWs* w) {
+  Carver cv(ws, 0);
+  w->perm = cv.take<int32_t>(n);
+  w->offsets = cv.take<int32_t>(k + 1);
+  w->gb = reduce_group_ws(n, k);
+  w->gws = cv.take<char>(w->gb);
+  return cv.off + 1024;
 }
 }  // namespace
 }  // namespace gdd
@@ -1947,10 +1987,8 @@ extern "C" size_t gdd_lloyd_reduce_words(int dim, int k) {
 }
 
 extern "C" size_t gdd_lloyd_reduce_ws_bytes(int64_t n, int dim, int k) {
-  n = std::max<int64_t>(n, 1);
-  k = std::max(k, 1);
-  return align256(sizeof(int32_t) * (size_t)n) + align256(sizeof(int32_t) * (size_t)(k + 1)) +
-         reduce_group_ws(n, k) + 1024;
+  ReduceWs w;
+  return carve_reduce(nullptr, std::max<int64_t>(n, 1), std::max(k, 1), &w);
 }
 
 extern "C" int gdd_lloyd_reduce_exponents(int64_t n, int dim, const float* X, int32_t* exps,
@@ -1976,14 +2014,12 @@ extern "C" int gdd_lloyd_reduce_local(int64_t n, int64_t r0, int64_t r1, int dim
                   X && labels && labels_old && exps && buf && state && ws && it >= 0,
               "lloyd_reduce_local: bad arguments");
   hipStream_t s = to_hip(stream);
-  if (ws_bytes < gdd_lloyd_reduce_ws_bytes(n, dim, k))
+  ReduceWs rw;
+  if (ws_bytes < carve_reduce(ws, n, k, &rw))
     return fail(GDD_E_WORKSPACE, "lloyd_reduce_local: workspace too small");
-  Carver cv(ws, ws_bytes);
-  int32_t* perm = cv.take<int32_t>(n);
-  int32_t* offsets = cv.take<int32_t>(k + 1);
-  const size_t gb = reduce_group_ws(n, k);
-  void* gws = cv.take<char>(gb);
-  if (!cv.ok()) return fail(GDD_E_WORKSPACE, "lloyd_reduce_local: workspace too small");
+  int32_t *perm = rw.perm, *offsets = rw.offsets;
+  const size_t gb = rw.gb;
+  void* gws = rw.gws;
   LloydState* st = static_cast<LloydState*>(state);
   const int sa = 2 * it;
   long long* b64 = reinterpret_cast<long long*>(buf);

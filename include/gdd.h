@@ -371,6 +371,11 @@ size_t gdd_kmeans_plusplus_ws_bytes(int64_t n, int dim, int n_trials);  /* bound
 /* the workspace for this k: the n x n distance tables only where they are built (the multi-block  */
 /* table when (k - 1) 2.5e7 >= n^2 dim, i.e. when the rounds it saves cover its one-off build)      */
 size_t gdd_kmeans_plusplus_ws_bytes_k(int64_t n, int dim, int n_trials, int k);
+/* the launch path this shape takes under the current GDD_FORCE, by name (host only, no device call): */
+/* first_only, single_table_pair, single_table, single_fused/seq|blas, single_two_launch/seq|blas,    */
+/* split, big_pair, big, block_table, block/seq|blas; "invalid" for a shape gdd_kmeans_plusplus       */
+/* refuses. A static string.                                                                          */
+const char* gdd_kmeans_plusplus_path(int64_t n, int dim, int n_trials, int k);
 int gdd_kmeans_plusplus(int64_t n, int dim, const float* X, const float* w, int k, int n_trials,
                         int64_t first_id, const double* uniforms, float* centers, int64_t* indices,
                         void* ws, size_t ws_bytes, gdd_stream_t stream);

@@ -386,3 +386,48 @@ def test_kmeans_plusplus_split_rounds_match_block_rounds(monkeypatch, n, dim, k,
     c2, idx2 = _kpp_dev(X, k, T, 7, u, w=w)
     assert np.array_equal(idx, idx2)
     assert np.array_equal(bits(c), bits(c2))
+
+
+# one small shape per launch path (tests/test_kpp_plan_host.py has the whole table)
+GUARD_CASES = [
+    # (n, dim, T, k, GDD_FORCE tokens, path)
+    (100, 16, 4, 20, (), "single_table_pair"),
+    (1000, 16, 9, 16, (), "single_table"),
+    (1000, 16, 4, 15, (), "single_fused/seq"),
+    (3000, 400, 4, 20, (), "single_fused/blas"),
+    (1000, 16, 4, 16, ("kpp_no_table", "kpp_two_launch"), "single_two_launch/seq"),
+    (3000, 600, 4, 20, (), "single_two_launch/blas"),
+    (530000, 8, 4, 16, (), "split"),
+    (4097, 8, 4, 20, (), "big_pair"),
+    (4097, 8, 4, 20, ("kpp_force_table", "kpp_single_round"), "big"),
+    (4097, 8, 4, 20, ("kpp_force_table", "kpp_no_big1"), "block_table"),
+    (4097, 64, 4, 20, (), "block/seq"),
+    (4000, 40, 1, 8, (), "block/blas"),
+]
+
+
+@pytest.mark.parametrize("n,dim,T,k,toks,path", GUARD_CASES)
+def test_kmeans_plusplus_stays_inside_its_workspace(monkeypatch, n, dim, T, k, toks, path):
+    """Every launch path inside exactly the workspace the k-aware query promises: the seeding of the
+    ordinary call (which gets the k-free bound), the 4096 bytes behind the workspace untouched, and
+    the path the plan names is the intended one."""
+    force(monkeypatch, *toks)
+    lib = _lib.device_lib()
+    assert lib.gdd_kmeans_plusplus_path(n, dim, T, k).decode() == path
+    rng = np.random.default_rng(n + dim + T + k)
+    X = np.ascontiguousarray(rng.standard_normal((n, dim)), np.float32)
+    u = np.random.RandomState(n + k).uniform(size=(k - 1) * T)
+    c_ref, idx_ref = _kpp_dev(X, k, T, 3, u)
+    nbytes = lib.gdd_kmeans_plusplus_ws_bytes_k(n, dim, T, k)
+    Xd = torch.from_numpy(X).cuda()
+    ud = torch.from_numpy(u).cuda()
+    centers = torch.empty((k, dim), dtype=torch.float32, device="cuda")
+    idx = torch.empty(k, dtype=torch.int64, device="cuda")
+    ws = torch.full((nbytes + 4096,), 0xFF, dtype=torch.uint8, device="cuda")
+    rc = lib.gdd_kmeans_plusplus(n, dim, Xd.data_ptr(), None, k, T, 3, ud.data_ptr(), centers.data_ptr(),
+                                 idx.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr(Xd.device))
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert np.array_equal(idx.cpu().numpy(), idx_ref)
+    assert np.array_equal(bits(centers.cpu().numpy()), bits(c_ref))
+    assert bool((ws[nbytes:] == 0xFF).all())
