@@ -46,11 +46,6 @@ typedef float floatx4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
-inline size_t bf16q_lds(int ktiles, int nsteps, int dim, int waves) {
-  return (size_t)ktiles * nsteps * 64 * 16 + (size_t)ktiles * 32 * sizeof(float) +
-         (size_t)waves * (32 * dim + 16) * sizeof(float);
-}
-
 // the key: acc's bits with the in-tile index in the 5 low significand bits (one v_and_or_b32). Plain C,
 // not inline asm: an asm operand that reads an MFMA result directly is invisible to the compiler's
 // hazard recognizer (no wait states after the MFMA: stale accumulator values — r06, measured)
@@ -278,21 +273,32 @@ bool bf16q_norms_fit(int dim, int k) {
   return (int64_t)ktiles * 32 * 2 * nsteps <= (int64_t)4 * (32 * dim + 16);  // the 4-wave slots
 }
 
+size_t bf16q_lds(int dim, int k, int waves) {
+  const int nsteps = (dim + 15) / 16, ktiles = (k + 31) / 32;
+  return (size_t)ktiles * nsteps * 64 * 16 + (size_t)ktiles * 32 * sizeof(float) +
+         (size_t)waves * (32 * dim + 16) * sizeof(float);
+}
+
+// at three k-steps (the configs' logit widths 41 .. 47) with many centre tiles, 8-wave blocks with
+// one tile's loads in flight and at most 128 VGPRs (4 waves per SIMD): Reddit's k = 769 at 0.84 of
+// the 4-wave form's time, products' k = 196 the same within noise (r06, tools/micro_bf16.py).
+// want = 4 or 8: either form at any k (A/B, tests)
+int bf16q_waves(int dim, int k, int want) {
+  const int nsteps = (dim + 15) / 16, ktiles = (k + 31) / 32;
+  const bool f3 = nsteps == 3 && dim % 4 != 0 && (8 * dim + 63) / 64 == 6;
+  return f3 && want != 4 && (ktiles > 8 || want == 8) ? 8 : 4;
+}
+
 int bf16q_launch(int64_t n, int dim, const float* X, int k, const float* C, const float* c_norm2,
-                 int32_t* labels, float* sq_dist, hipStream_t s) {
+                 int32_t* labels, float* sq_dist, int waves, hipStream_t s) {
   const int nsteps = (dim + 15) / 16, ktiles = (k + 31) / 32;
   GDD_REQUIRE(n >= 32 && dim % 16 != 0 && nsteps <= 4 && k > 0, "bf16 labels pass: unsupported shape");
   GDD_REQUIRE((reinterpret_cast<uintptr_t>(X) & 15) == 0, "bf16 labels pass: X must be 16-byte aligned");
   GDD_REQUIRE(c_norm2 || bf16q_norms_fit(dim, k), "bf16 labels pass: this k needs the norms given");
-  // at three k-steps (the configs' logit widths 41 .. 47) with many centre tiles, 8-wave blocks with
-  // one tile's loads in flight and at most 128 VGPRs (4 waves per SIMD): Reddit's k = 769 at 0.84 of
-  // the 4-wave form's time, products' k = 196 the same within noise (r06, tools/micro_bf16.py).
-  // GDD_FORCE=bf16_w4 / bf16_w8: either form at any k (A/B, tests)
-  const bool f3 = nsteps == 3 && dim % 4 != 0 && (8 * dim + 63) / 64 == 6;
-  const bool w8 = f3 && !forced("bf16_w4") && (ktiles > 8 || forced("bf16_w8"));
-  const int waves = w8 ? 8 : 4;
-  const size_t lds = bf16q_lds(ktiles, nsteps, dim, waves);
-  GDD_REQUIRE(lds <= 150 * 1024, "bf16 labels pass: centres do not fit the LDS");
+  const bool w8 = waves == 8;
+  GDD_REQUIRE(w8 ? bf16q_waves(dim, k, 8) == 8 : waves == 4, "bf16 labels pass: no %d-wave form here", waves);
+  const size_t lds = bf16q_lds(dim, k, waves);
+  GDD_REQUIRE(lds <= kAssignLdsBudget, "bf16 labels pass: centres do not fit the LDS");
   const int64_t ntiles = (n + 31) / 32;
   const int per_need = (8 * dim + 63) / 64;
   auto go = [&](auto kern) -> int {

@@ -87,10 +87,17 @@ int sort_pairs_i32(const int32_t* keys_in, int32_t* keys_out, const int32_t* val
 // ---------------------------------------------------------------------------------------------
 // resident workgroups of a kernel on the current device (occupancy x CUs; cached)
 int occupancy_blocks(const void* fn, int threads, size_t lds, int* out);
+// one block's LDS in the labels passes that stage every centre: 10 KiB of the CU's 160 are left free
+constexpr size_t kAssignLdsBudget = 150 * 1024;
 // the bf16 full labels pass's r06 kernel (gdd_bf16.hip): n >= 32, dim <= 64 and not a multiple of 16,
-// 16-byte aligned X, whole rows; one launch, no workspace (c_norm2 may be null if bf16q_norms_fit)
+// 16-byte aligned X, whole rows; one launch, no workspace (c_norm2 may be null if bf16q_norms_fit).
+// waves: 4 or 8 per block, assign_plan's choice (gdd_kmeans.hip) from the two functions below
 int bf16q_launch(int64_t n, int dim, const float* X, int k, const float* C, const float* c_norm2,
-                 int32_t* labels, float* sq_dist, hipStream_t s);
+                 int32_t* labels, float* sq_dist, int waves, hipStream_t s);
+// its LDS bytes at that many waves, and the wave count it prefers whatever the LDS (want: 0, or 4 or
+// 8 to force that form where the kernel has it)
+size_t bf16q_lds(int dim, int k, int waves);
+int bf16q_waves(int dim, int k, int want);
 // whether bf16q_launch can take the centres' norms itself (c_norm2 null) at this dim and k
 bool bf16q_norms_fit(int dim, int k);
 
@@ -98,7 +105,8 @@ bool bf16q_norms_fit(int dim, int k);
 // other shapes take by default (so its bits can be pinned on a small shape), e.g.
 // GDD_FORCE=kpp_no_table,lloyd_no_prune or GDD_FORCE=kpp_big1_max=32768. Read on every call (host).
 // The kpp_* tokens are read in one place, kpp_plan (gdd_kmeanspp.hip), which turns them into the
-// launch path that gdd_kmeans_plusplus_path names.
+// launch path that gdd_kmeans_plusplus_path names; the bf16_* tokens likewise in assign_plan
+// (gdd_kmeans.hip) and gdd_kmeans_assign_path.
 //   kpp_no_table      k-means++ without the n x n distance table (small and multi-block plans)
 //   kpp_force_table   the multi-block table although kpp_table_pays says no (small k)
 //   kpp_no_big1       the per-block table rounds instead of one workgroup per trial (n <= 16,384)
@@ -115,7 +123,8 @@ bool bf16q_norms_fit(int dim, int k);
 //   group_split       the multi-launch label grouping where the one-launch form fits
 //   center_seq        KMeans' centring by the sequential column chains
 //   bf16_v1           the r03 bf16 labels pass (gdd_kmeans.hip) instead of the r06 one (gdd_bf16.hip)
-//   bf16_w4, bf16_w8  the r06 pass's 4- or 8-wave block form at any k (dims 41 .. 47)
+//   bf16_w4, bf16_w8  the r06 pass's 4- or 8-wave block form at any k (dims 41 .. 47); 8 waves only
+//                     where their LDS fits, else 4
 //   hop_row_order     the propagation's work list in row order (no longest-first schedule)
 //   hop_no_probe      longest first even where the locality probe would pick row order
 //   hop_relabel_len   the relabelled hops' work list longest first instead of in the new order

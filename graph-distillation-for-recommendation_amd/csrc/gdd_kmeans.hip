@@ -998,17 +998,11 @@ template <int WAVES, bool VEC>
 __global__ __launch_bounds__(64 * WAVES) void k_assign_small(
     int64_t n, int dim, int dimp, const float* __restrict__ X, const int64_t* __restrict__ rows,
     int k, const float* __restrict__ C, const float* __restrict__ cn2, int32_t* __restrict__ labels,
-    float* __restrict__ sq_dist, const int32_t* __restrict__ stop, int step_i, RngNext rn) {
+    float* __restrict__ sq_dist, const int32_t* __restrict__ stop, int step_i) {
   if (stopped(stop, step_i)) return;
   GDD_STAMP_WHEN(g_stamps_kmeans, (threadIdx.x == 0 && blockIdx.x == 0), 0);
   constexpr int kTileU = WAVES == 16 ? 6 : 8;  // 16 waves: 128 VGPRs per lane, fewer loads in flight
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  if (rn.rows && blockIdx.x == gridDim.x - 1) {
-    // extra workgroup: the next step's batch indices (randint(0, n, b)) from the device MT state,
-    // concurrently with this step's assignment
-    mt_randint_from(rn.in, reinterpret_cast<uint32_t*>(lds), 0, rn.n, rn.bs, rn.rows, rn.out);
-    return;
-  }
   const int S = dimp + 1;
   float* Pl = lds;                                 // 32 points x S
   float* Cl = Pl + 32 * S;                         // WAVES x 32 centres x S (consecutive tiles)
@@ -1614,6 +1608,16 @@ int gdd::occupancy_blocks(const void* fn, int threads, size_t lds, int* out) {
 }
 namespace {
 
+// the opt-in above the 64 KiB default of dynamic LDS (gfx950 has 160 KiB per CU), on every launch
+int lds_opt_in(const void* fn, size_t lds) {
+  if (lds > 65536)
+    GDD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return GDD_OK;
+}
+
+// ---- the labels pass on the host: one plan, one launcher per kernel form -------------------------
+// (labels pass, has the path table)
+
 // LDS bytes of k_assign for a given geometry
 size_t assign_lds(int waves, int dimp, int cch) {
   const int S = dimp + 1;
@@ -1621,187 +1625,372 @@ size_t assign_lds(int waves, int dimp, int cch) {
   return sizeof(float) * ((size_t)ncp * S + (size_t)32 * waves * S + ncp);
 }
 
-constexpr size_t kLdsCap = 160 * 1024;
+constexpr size_t kLdsCap = 160 * 1024;  // a CU's LDS (gfx950)
+// the fused small-batch kernel: one block per 32 points, up to this many rows
+constexpr int64_t kSmallMaxRows = 16384;
+// persistent blocks: all centres in one chunk when they fit 2 blocks per CU, else the fewest
+// chunks that do; about two blocks per CU walk the point tiles
+constexpr size_t kPersistLdsBudget = 78 * 1024;
+constexpr int kPersistBlocks = 512;
+// tiles: centers per block: as many as fit the LDS budget (>= 32), then fewer while the grid is too
+// small to occupy 256 CUs
+constexpr size_t kTilesLdsBudget = 65536, kTilesLdsBudgetWide = 160000;  // wide: dims above 224
+constexpr int64_t kTilesMinBlocks = 1024;
 
-bool use_small_assign(int64_t n, int dim) {
-  return n <= 16384 && assign_small_lds(4, dim) <= kLdsCap;
+enum AssignPath {
+  ASSIGN_INVALID,     // a shape the entry point refuses, or a grid or LDS past the device's limits
+  ASSIGN_SMALL,       // k_assign_small<W, VEC>
+  ASSIGN_WAVES,       // k_assign_waves<2, W, CONTIG, 6, TOP2, ROW4> (+ k_assign_finalize without TOP2)
+  ASSIGN_PERSIST,     // k_assign_persist<2> + k_assign_finalize
+  ASSIGN_TILES,       // k_assign<W, VEC> + k_assign_finalize
+  ASSIGN_BF16Q,       // bf16q_launch (gdd_bf16.hip, r06)
+  ASSIGN_BF16P,       // k_bf16_frags + k_assign_bf16p<PER> (r03)
+  ASSIGN_BF16_TILES,  // k_assign_bf16<4> + k_assign_finalize
+};
+
+// Everything the host decides about one labels pass, from (n, dim, k), the GDD_ASSIGN_* flags
+// (gdd.h), the workspace size (bf16 only) and GDD_FORCE alone.
+struct AssignPlan {
+  AssignPath path;
+  bool top2;    // the Lloyd loop's bounded E-step: keys and second distances, no labels
+  int waves;    // waves per block
+  bool vec;     // small, tiles: float4 loads (dim % 4 == 0, X and C 16-byte aligned)
+  bool contig;  // waves: point tiles are contiguous spans of X (no row list, X 16-byte aligned)
+  bool row4;    // waves, top-2: a row list over the padded copy, 16-byte pieces of aligned rows
+  int dimp;     // row width: even (small, waves), 16-padded (persist, tiles, bf16 tiles)
+  int cch, gy;  // centres per chunk; chunks (grid.y)
+  int64_t gx;   // grid.x ...
+  bool cap_resident;  // ... at most the kernel's resident blocks / gy, so each walks several tiles
+  size_t lds;
+  bool prefill;       // k_fill_u64 over the keys before the launch
+  // the persistent form's chunking (dimp16, 4 waves, kPersistLdsBudget), computed for every dim <= 96:
+  int cch_persist;       // the wave tiles take it as their own chunk when no wave count holds all centres
+  bool prefill_persist;  // the wave tiles prefill when it has two chunks or more, whatever their own count
+  bool need_norms;  // the form reads c_norm2 (bf16: computed first when the caller gave none)
+  int nsteps, ktiles, per_need;  // bf16: 16-feature k-steps, 32-centre tiles, float4 loads per lane per tile
+};
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int assign_flags(const float* X, const float* C, const int64_t* rows) {
+  return (rows ? GDD_ASSIGN_ROWS : 0) | (aligned16(X) ? 0 : GDD_ASSIGN_X_UNALIGNED) |
+         (aligned16(C) ? 0 : GDD_ASSIGN_C_UNALIGNED);
 }
 
-template <int W, bool VEC>
-int launch_assign_small_t(int64_t n, int dim, const float* X, const int64_t* rows, int k,
-                          const float* C, const float* cn2, int32_t* labels, float* sq_dist,
-                          const int32_t* stop, int step_i, const RngNext& rn, hipStream_t s) {
-  const int dimp = (dim + 1) & ~1;
-  const size_t lds = std::max(assign_small_lds(W, dim), kMtRingBytes + 64);
-  if (lds > 65536)
-    GDD_HIP(hipFuncSetAttribute((const void*)k_assign_small<W, VEC>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const unsigned grid = (unsigned)((n + 31) / 32) + (rn.rows ? 1u : 0u);
-  k_assign_small<W, VEC><<<grid, 64 * W, lds, s>>>(n, dim, dimp, X, rows, k, C, cn2, labels,
-                                                   sq_dist, stop, step_i, rn);
+// tiles and bf16 tiles: cch as large as `budget` allows, then smaller while the grid is short
+bool plan_tiles(AssignPlan& p, int64_t n, int k, size_t budget, size_t (*lds_of)(int, int, int)) {
+  p.gx = (n + 32 * p.waves - 1) / (32 * p.waves);
+  const int kp = (k + 31) & ~31;
+  int cch = 32;
+  while (cch + 32 <= kp && lds_of(p.waves, p.dimp, cch + 32) <= budget) cch += 32;
+  int64_t gy = (k + cch - 1) / cch;
+  while (p.gx * gy < kTilesMinBlocks && cch > 32) {
+    cch -= 32;
+    gy = (k + cch - 1) / cch;
+  }
+  p.cch = cch;
+  p.gy = (int)gy;
+  p.lds = lds_of(p.waves, p.dimp, cch);
+  p.prefill = true;
+  p.need_norms = true;
+  return p.gx < (1ll << 31) && gy < 65536 && p.lds <= kLdsCap;
+}
+
+// The one place that reads GDD_FORCE's bf16_* tokens. ws_bytes: the bf16 forms' workspace (the r03
+// fragments live in it); the fp32 forms take theirs as checked.
+AssignPlan assign_plan(int64_t n, int dim, int k, int flags, size_t ws_bytes) {
+  AssignPlan p{};
+  p.path = ASSIGN_INVALID;
+  p.gy = 1;
+  if (n <= 0 || dim <= 0 || k <= 0) return p;
+  const bool rows = flags & GDD_ASSIGN_ROWS, x_al = !(flags & GDD_ASSIGN_X_UNALIGNED);
+  const bool xc_al = x_al && !(flags & GDD_ASSIGN_C_UNALIGNED);
+  const int dimp16 = (dim + 15) & ~15;  // zero-padded rows: unguarded groups of 8 MFMA steps
+  const int dimpw = (dim + 1) & ~1;     // even row width: the K = 2 steps (r05; was 16-padded)
+  const int kp = (k + 31) & ~31, kt = (k + 31) / 32;
+  p.top2 = flags & GDD_ASSIGN_TOP2;
+  p.vec = dim % 4 == 0 && xc_al;
+  p.contig = !rows && x_al;
+
+  if (flags & GDD_ASSIGN_BF16) {
+    if (p.top2 || dim > 512) return p;
+    p.nsteps = dimp16 / 16;
+    p.ktiles = kt;
+    p.per_need = (8 * dim + 63) / 64;
+    p.waves = 4;
+    p.need_norms = true;
+    // the persistent kernels: whole rows (no gathered rows), dim <= 128, centre fragments fit LDS
+    // (the r03 kernel's) and the workspace
+    const size_t lds_p = assign_bf16p_lds(kt, p.nsteps, dim);
+    if (p.contig && dim <= 128 && lds_p <= kAssignLdsBudget && bf16_frag_bytes(kt, p.nsteps) <= ws_bytes) {
+      p.cap_resident = true;
+      // the r06 kernel (gdd_bf16.hip) where its shapes allow; GDD_FORCE=bf16_v1: the r03 kernel (A/B).
+      // GDD_FORCE=bf16_w4 / bf16_w8: either block form at any k (A/B, tests). Never a form whose LDS
+      // does not fit: 8 waves, else 4, else r03
+      if (!forced("bf16_v1") && n >= 32 && p.nsteps <= 4 && dim % 16 != 0) {
+        int w = bf16q_waves(dim, k, forced("bf16_w4") ? 4 : forced("bf16_w8") ? 8 : 0);
+        if (w == 8 && bf16q_lds(dim, k, 8) > kAssignLdsBudget) w = 4;
+        if (bf16q_lds(dim, k, w) <= kAssignLdsBudget) {
+          p.path = ASSIGN_BF16Q;
+          p.waves = w;
+          p.lds = bf16q_lds(dim, k, w);
+          p.gx = ((n + 31) / 32 + w - 1) / w;
+          p.need_norms = !bf16q_norms_fit(dim, k);
+          return p;
+        }
+      }
+      p.path = ASSIGN_BF16P;
+      p.lds = lds_p;
+      p.gx = ((n + 31) / 32 + 3) / 4;
+      return p;
+    }
+    p.dimp = dimp16;
+    if (plan_tiles(p, n, k, kTilesLdsBudget, assign_bf16_lds)) p.path = ASSIGN_BF16_TILES;
+    return p;
+  }
+
+  // wave tiles: as many waves per block as the LDS holds with every centre in one chunk (the
+  // centre chunk is staged once per block), at least 4; else the persistent form's chunks.
+  // 12 waves (768 threads) leave 170 registers per lane: two chains and the prefetched tile
+  // without spills, three waves per SIMD
+  int wn = 0;
+  if (dimp16 <= 48)  // wave tiles: dim <= 48 (every config's k-means input)
+    for (int wv : {12, 8, 4})
+      if (wn == 0 && assign_lds(wv, dimpw, kp) <= kAssignLdsBudget) wn = wv;
+  if (p.top2) {  // the bounded E-step needs every centre in one chunk; it has no small form
+    if (!wn) return p;
+    p.path = ASSIGN_WAVES;
+    p.row4 = !p.contig && (flags & GDD_ASSIGN_PADDED);
+    p.waves = wn;
+    p.dimp = dimpw;
+    p.cch = kp;
+    p.need_norms = true;
+  } else if (n <= kSmallMaxRows && assign_small_lds(4, dim) <= kLdsCap) {
+    // one 32-centre tile per wave when LDS allows (k <= 512), else fewer waves looping over tiles
+    p.path = ASSIGN_SMALL;
+    p.waves = kt > 8 && assign_small_lds(16, dim) <= kLdsCap ? 16
+              : kt > 4 && assign_small_lds(8, dim) <= kLdsCap ? 8 : 4;
+    p.dimp = dimpw;
+    p.gx = (n + 31) / 32;
+    p.lds = assign_small_lds(p.waves, dim);
+    return p;
+  } else if (dimp16 <= 96) {
+    p.need_norms = true;
+    int chunks = 1;
+    while (chunks < kt && assign_lds(4, dimp16, ((kt + chunks - 1) / chunks) * 32) > kPersistLdsBudget) ++chunks;
+    p.cch_persist = ((kt + chunks - 1) / chunks) * 32;
+    p.prefill_persist = (k + p.cch_persist - 1) / p.cch_persist > 1;
+    if (dimp16 > 48) {
+      p.path = ASSIGN_PERSIST;
+      p.waves = 4;
+      p.dimp = dimp16;
+      p.cch = p.cch_persist;
+      p.gy = (k + p.cch - 1) / p.cch;
+      p.gx = std::min<int64_t>((n + 127) / 128, std::max(1, kPersistBlocks / p.gy));
+      p.lds = assign_lds(4, dimp16, p.cch);
+      p.prefill = p.gy > 1;
+      return p;
+    }
+    p.path = ASSIGN_WAVES;
+    p.waves = wn ? wn : 4;
+    p.dimp = dimpw;
+    p.cch = wn ? kp : p.cch_persist;
+    p.gy = (k + p.cch - 1) / p.cch;
+    p.prefill = p.gy > 1 || p.prefill_persist;
+  } else {
+    p.waves = dimp16 <= 224 ? 2 : 1;
+    p.dimp = dimp16;
+    if (plan_tiles(p, n, k, dimp16 <= 224 ? kTilesLdsBudget : kTilesLdsBudgetWide, assign_lds))
+      p.path = ASSIGN_TILES;
+    return p;
+  }
+  // wave tiles, both uses
+  p.lds = assign_lds(p.waves, p.dimp, p.cch);
+  p.gx = ((n + 31) / 32 + p.waves - 1) / p.waves;
+  p.cap_resident = true;
+  return p;
+}
+
+// e.g. waves/w12/contig/224x1, small/w16/vec, persist/128x2/prefill, bf16q/w8
+const char* assign_path_name(const AssignPlan& p) {
+  static thread_local char name[64];
+  const char* fill = p.prefill ? "/prefill" : "";
+  switch (p.path) {
+    case ASSIGN_INVALID: break;
+    case ASSIGN_SMALL: snprintf(name, sizeof name, "small/w%d/%s", p.waves, p.vec ? "vec" : "scalar"); return name;
+    case ASSIGN_WAVES:
+      snprintf(name, sizeof name, "%s/w%d/%s/%dx%d%s", p.top2 ? "waves_top2" : "waves", p.waves,
+               p.contig ? "contig" : p.row4 ? "row4" : "rows", p.cch, p.gy, fill);
+      return name;
+    case ASSIGN_PERSIST: snprintf(name, sizeof name, "persist/%dx%d%s", p.cch, p.gy, fill); return name;
+    case ASSIGN_TILES:
+      snprintf(name, sizeof name, "tiles/w%d/%s/%dx%d%s", p.waves, p.vec ? "vec" : "scalar", p.cch, p.gy, fill);
+      return name;
+    case ASSIGN_BF16Q: snprintf(name, sizeof name, "bf16q/w%d", p.waves); return name;
+    case ASSIGN_BF16P: snprintf(name, sizeof name, "bf16p/per%d", p.per_need); return name;
+    case ASSIGN_BF16_TILES: snprintf(name, sizeof name, "bf16_tiles/%dx%d%s", p.cch, p.gy, fill); return name;
+  }
+  return "invalid";
+}
+
+// ---- the launchers: the plan and the pointers ----------------------------------------------------
+struct AssignArgs {
+  int64_t n;  // top-2: the bound n_max of *n_dev
+  int dim;
+  const float* X;
+  const int64_t* rows;
+  int k;
+  const float *C, *cn2;
+  int32_t* labels;
+  float* sq_dist;
+  unsigned long long* keys;
+  const int32_t* stop;
+  int step_i;
+  // top-2 only: second distances out, the device row count, the padded copy and its row stride
+  float* sec;
+  const int64_t* n_dev;
+  const float* Xp;
+  int ldp;
+};
+
+int assign_prefill(const AssignPlan& p, const AssignArgs& a, hipStream_t s) {
+  if (!p.prefill) return GDD_OK;
+  k_fill_u64<<<blocks_for(a.n), 256, 0, s>>>(a.n, a.keys, ~0ull, a.stop, a.step_i);
   GDD_LAUNCHED();
   return GDD_OK;
 }
 
-template <bool VEC>
-int launch_assign_small(int64_t n, int dim, const float* X, const int64_t* rows, int k,
-                        const float* C, const float* cn2, int32_t* labels, float* sq_dist,
-                        const int32_t* stop, int step_i, const RngNext& rn, hipStream_t s) {
-  // one 32-centre tile per wave when LDS allows (k <= 512), else fewer waves looping over tiles
-  const int tiles = (k + 31) / 32;
-  if (tiles > 8 && assign_small_lds(16, dim) <= kLdsCap)
-    return launch_assign_small_t<16, VEC>(n, dim, X, rows, k, C, cn2, labels, sq_dist, stop, step_i,
-                                          rn, s);
-  if (tiles > 4 && assign_small_lds(8, dim) <= kLdsCap)
-    return launch_assign_small_t<8, VEC>(n, dim, X, rows, k, C, cn2, labels, sq_dist, stop, step_i,
-                                         rn, s);
-  return launch_assign_small_t<4, VEC>(n, dim, X, rows, k, C, cn2, labels, sq_dist, stop, step_i,
-                                       rn, s);
+int assign_finalize(const AssignArgs& a, hipStream_t s) {
+  k_assign_finalize<<<blocks_for(a.n), 256, 0, s>>>(a.n, a.dim, a.X, a.rows, a.C, a.keys, a.labels, a.sq_dist,
+                                                    a.stop, a.step_i);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+// grid.x: the plan's, under cap_resident at most the kernel's resident blocks per chunk
+int assign_grid_x(const AssignPlan& p, const void* fn, unsigned* gx) {
+  int64_t g = p.gx;
+  if (p.cap_resident) {
+    int res = 0;
+    if (const int rc = resident_blocks(fn, 64 * p.waves, p.lds, &res)) return rc;
+    g = std::min(g, std::max<int64_t>(1, (int64_t)res / p.gy));
+  }
+  *gx = (unsigned)g;
+  return GDD_OK;
+}
+
+template <int W>
+using Waves = std::integral_constant<int, W>;
+
+int assign_small(const AssignPlan& p, const AssignArgs& a, hipStream_t s) {
+  auto go = [&](auto kern) -> int {
+    if (const int rc = lds_opt_in((const void*)kern, p.lds)) return rc;
+    kern<<<(unsigned)p.gx, 64 * p.waves, p.lds, s>>>(a.n, a.dim, p.dimp, a.X, a.rows, a.k, a.C, a.cn2, a.labels,
+                                                     a.sq_dist, a.stop, a.step_i);
+    GDD_LAUNCHED();
+    return GDD_OK;
+  };
+  auto pick = [&](auto W_) -> int {
+    constexpr int W = decltype(W_)::value;
+    return p.vec ? go(k_assign_small<W, true>) : go(k_assign_small<W, false>);
+  };
+  return p.waves == 16 ? pick(Waves<16>()) : p.waves == 8 ? pick(Waves<8>()) : pick(Waves<4>());
+}
+
+int assign_waves(const AssignPlan& p, const AssignArgs& a, hipStream_t s) {
+  if (const int rc = assign_prefill(p, a, s)) return rc;
+  auto go = [&](auto kern) -> int {
+    if (const int rc = lds_opt_in((const void*)kern, p.lds)) return rc;
+    unsigned gx = 0;
+    if (const int rc = assign_grid_x(p, (const void*)kern, &gx)) return rc;
+    kern<<<dim3(gx, (unsigned)p.gy), 64 * p.waves, p.lds, s>>>(a.n, a.dim, p.dimp, p.row4 ? a.Xp : a.X, a.rows,
+                                                              a.k, a.C, a.cn2, p.cch, a.keys, a.stop, a.step_i,
+                                                              a.sec, a.n_dev, p.row4 ? a.ldp : 0);
+    GDD_LAUNCHED();
+    return GDD_OK;
+  };
+  auto pick = [&](auto W_) -> int {
+    constexpr int W = decltype(W_)::value;
+    if (!p.top2) return p.contig ? go(k_assign_waves<2, W, true, 6>) : go(k_assign_waves<2, W, false, 6>);
+    if (p.contig) return go(k_assign_waves<2, W, true, 6, true>);
+    // a row list over the padded copy: 16-byte pieces of aligned rows (F = 6 pieces per lane cover 48)
+    return p.row4 ? go(k_assign_waves<2, W, false, 6, true, true>) : go(k_assign_waves<2, W, false, 6, true>);
+  };
+  const int rc = p.waves == 12 ? pick(Waves<12>()) : p.waves == 8 ? pick(Waves<8>()) : pick(Waves<4>());
+  return (rc || p.top2) ? rc : assign_finalize(a, s);
+}
+
+int assign_persist(const AssignPlan& p, const AssignArgs& a, hipStream_t s) {
+  if (const int rc = assign_prefill(p, a, s)) return rc;
+  // two centre tiles per pass: four accumulator chains would need 292 registers, one wave per SIMD
+  // (measured 1.38 vs 0.91 ms at the products shape)
+  if (const int rc = lds_opt_in((const void*)k_assign_persist<2>, p.lds)) return rc;
+  k_assign_persist<2><<<dim3((unsigned)p.gx, (unsigned)p.gy), 256, p.lds, s>>>(
+      a.n, a.dim, p.dimp, a.X, a.rows, a.k, a.C, a.cn2, p.cch, a.keys, a.stop, a.step_i);
+  GDD_LAUNCHED();
+  return assign_finalize(a, s);
+}
+
+int assign_tiles(const AssignPlan& p, const AssignArgs& a, hipStream_t s) {
+  if (const int rc = assign_prefill(p, a, s)) return rc;
+  auto go = [&](auto kern) -> int {
+    if (const int rc = lds_opt_in((const void*)kern, p.lds)) return rc;
+    kern<<<dim3((unsigned)p.gx, (unsigned)p.gy), 64 * p.waves, p.lds, s>>>(
+        a.n, a.dim, p.dimp, a.X, a.rows, a.k, a.C, a.cn2, p.cch, a.keys, a.stop, a.step_i);
+    GDD_LAUNCHED();
+    return GDD_OK;
+  };
+  const int rc = p.waves == 2 ? (p.vec ? go(k_assign<2, true>) : go(k_assign<2, false>))
+                              : (p.vec ? go(k_assign<1, true>) : go(k_assign<1, false>));
+  return rc ? rc : assign_finalize(a, s);
+}
+
+int assign_bf16p(const AssignPlan& p, const AssignArgs& a, void* ws, hipStream_t s) {
+  bf16x8_t* frags = static_cast<bf16x8_t*>(ws);  // the keys are not used on this path
+  float* cn = reinterpret_cast<float*>(static_cast<char*>(ws) + (size_t)p.ktiles * p.nsteps * 64 * 16);
+  const int nfr = std::max(p.ktiles * p.nsteps * 64, p.ktiles * 32);
+  k_bf16_frags<<<(nfr + 255) / 256, 256, 0, s>>>(a.dim, p.nsteps, p.ktiles, a.k, a.C, a.cn2, frags, cn);
+  GDD_LAUNCHED();
+  auto go = [&](auto kern) -> int {
+    if (const int rc = lds_opt_in((const void*)kern, p.lds)) return rc;
+    unsigned gx = 0;
+    if (const int rc = assign_grid_x(p, (const void*)kern, &gx)) return rc;
+    kern<<<gx, 256, p.lds, s>>>(a.n, a.dim, p.nsteps, p.ktiles, a.X, a.k, frags, cn, a.C, a.labels, a.sq_dist);
+    GDD_LAUNCHED();
+    return GDD_OK;
+  };
+  if (p.per_need <= 1) return go(k_assign_bf16p<1>);
+  if (p.per_need <= 2) return go(k_assign_bf16p<2>);
+  if (p.per_need <= 4) return go(k_assign_bf16p<4>);
+  if (p.per_need <= 6) return go(k_assign_bf16p<6>);
+  if (p.per_need <= 8) return go(k_assign_bf16p<8>);
+  if (p.per_need <= 12) return go(k_assign_bf16p<12>);
+  return go(k_assign_bf16p<16>);
+}
+
+int assign_bf16_tiles(const AssignPlan& p, const AssignArgs& a, hipStream_t s) {
+  if (const int rc = assign_prefill(p, a, s)) return rc;
+  k_assign_bf16<4><<<dim3((unsigned)p.gx, (unsigned)p.gy), 64 * 4, p.lds, s>>>(a.n, a.dim, p.dimp, a.X, a.rows,
+                                                                             a.k, a.C, a.cn2, p.cch, a.keys);
+  GDD_LAUNCHED();
+  return assign_finalize(a, s);
 }
 
 // labels (+ optional per-sample sq_dist) of n samples against k centres.
 // small n: fused k_assign_small; large n: centre chunks over grid.y + 64-bit atomicMin keys.
-// rn.rows != nullptr (small n only): the launch also draws the next batch (see RngNext).
 int launch_assign(int64_t n, int dim, const float* X, const int64_t* rows, int k, const float* C,
                   const float* c_norm2, int32_t* labels, float* sq_dist,
-                  unsigned long long* keys, const int32_t* stop, int step_i, hipStream_t s,
-                  const RngNext& rn = RngNext{nullptr, nullptr, nullptr, 0, 0}) {
-  if (use_small_assign(n, dim)) {
-    const bool vec = (dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(C)) & 15) == 0;
-    return vec ? launch_assign_small<true>(n, dim, X, rows, k, C, c_norm2, labels, sq_dist, stop,
-                                           step_i, rn, s)
-               : launch_assign_small<false>(n, dim, X, rows, k, C, c_norm2, labels, sq_dist, stop,
-                                            step_i, rn, s);
+                  unsigned long long* keys, const int32_t* stop, int step_i, hipStream_t s) {
+  const AssignPlan p = assign_plan(n, dim, k, assign_flags(X, C, rows), 0);
+  GDD_REQUIRE(p.path != ASSIGN_INVALID, "assign: n=%lld dim=%d k=%d: grid or LDS too large", (long long)n, dim, k);
+  GDD_REQUIRE(!p.need_norms || (c_norm2 && keys), "assign: large-n path needs c_norm2 and the key workspace");
+  const AssignArgs a{n, dim, X, rows, k, C, c_norm2, labels, sq_dist, keys, stop, step_i, nullptr, nullptr, nullptr, 0};
+  switch (p.path) {
+    case ASSIGN_SMALL: return assign_small(p, a, s);
+    case ASSIGN_WAVES: return assign_waves(p, a, s);
+    case ASSIGN_PERSIST: return assign_persist(p, a, s);
+    default: return assign_tiles(p, a, s);
   }
-  GDD_REQUIRE(!rn.rows, "assign: in-launch batch draws need the small-batch path");
-  GDD_REQUIRE(c_norm2 && keys, "assign: large-n path needs c_norm2 and the key workspace");
-  const int dimp16 = (dim + 15) & ~15;  // zero-padded rows: unguarded groups of 8 MFMA steps
-  if (dimp16 <= 96) {
-    // persistent blocks: all centres in one chunk when they fit 2 blocks per CU, else the fewest
-    // chunks that do; about two blocks per CU walk the point tiles
-    const int kt = (k + 31) / 32;
-    int chunks = 1;
-    while (chunks < kt && assign_lds(4, dimp16, ((kt + chunks - 1) / chunks) * 32) > 78 * 1024) ++chunks;
-    const int cch = ((kt + chunks - 1) / chunks) * 32;
-    const int gy = (k + cch - 1) / cch;
-    const int64_t ntiles = (n + 127) / 128;
-    const int64_t gx = std::min<int64_t>(ntiles, std::max<int64_t>(1, 512 / gy));
-    const size_t lds = assign_lds(4, dimp16, cch);
-    if (gy > 1) {
-      k_fill_u64<<<blocks_for(n), 256, 0, s>>>(n, keys, ~0ull, stop, step_i);
-      GDD_LAUNCHED();
-    }
-    auto go = [&](auto kern) -> int {
-      if (lds > 65536)
-        GDD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      kern<<<dim3((unsigned)gx, (unsigned)gy), 256, lds, s>>>(n, dim, dimp16, X, rows, k, C, c_norm2, cch,
-                                                              keys, stop, step_i);
-      GDD_LAUNCHED();
-      return GDD_OK;
-    };
-    // two centre tiles per pass: four accumulator chains would need 292 registers, one wave per SIMD
-    // (measured 1.38 vs 0.91 ms at the products shape)
-    int rc0;
-    if (dimp16 > 48) {  // wave tiles: dim <= 48 (every config's k-means input)
-      rc0 = go(k_assign_persist<2>);
-    } else {
-      // wave tiles: as many waves per block as the LDS holds with every centre in one chunk (the
-      // centre chunk is staged once per block), at least 4; else the persistent form's chunks.
-      // 12 waves (768 threads) leave 170 registers per lane: two chains and the prefetched tile
-      // without spills, three waves per SIMD
-      const int dimpw = (dim + 1) & ~1;  // even row width: the K = 2 steps (r05; was 16-padded)
-      int Wn = 0;
-      for (int wv : {12, 8, 4})
-        if (Wn == 0 && assign_lds(wv, dimpw, (k + 31) & ~31) <= 150 * 1024) Wn = wv;
-      const int cchw = Wn ? ((k + 31) & ~31) : cch;
-      if (!Wn) Wn = 4;
-      const int gyw = (k + cchw - 1) / cchw;
-      const size_t ldsw = assign_lds(Wn, dimpw, cchw);
-      const int64_t wtiles = (n + 31) / 32;
-      const bool contig = rows == nullptr && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-      if (gyw > 1 && gy == 1) {
-        k_fill_u64<<<blocks_for(n), 256, 0, s>>>(n, keys, ~0ull, stop, step_i);
-        GDD_LAUNCHED();
-      }
-      auto gow = [&](auto kern, int wv) -> int {
-        if (ldsw > 65536)
-          GDD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw));
-        int res = 0;
-        const int rrc = resident_blocks((const void*)kern, 64 * wv, ldsw, &res);
-        if (rrc) return rrc;
-        const int64_t per = std::max<int64_t>(1, (int64_t)res / gyw);
-        const int64_t gxw = std::min<int64_t>((wtiles + wv - 1) / wv, per);
-        kern<<<dim3((unsigned)gxw, (unsigned)gyw), 64 * wv, ldsw, s>>>(n, dim, dimpw, X, rows, k, C,
-                                                                      c_norm2, cchw, keys, stop, step_i,
-                                                                      nullptr, nullptr, 0);
-        GDD_LAUNCHED();
-        return GDD_OK;
-      };
-      auto pick = [&](auto W_) -> int {
-        constexpr int Wc = decltype(W_)::value;
-        return contig ? gow(k_assign_waves<2, Wc, true, 6>, Wc) : gow(k_assign_waves<2, Wc, false, 6>, Wc);
-      };
-      if (Wn == 12)
-        rc0 = pick(std::integral_constant<int, 12>());
-      else if (Wn == 8)
-        rc0 = pick(std::integral_constant<int, 8>());
-      else
-        rc0 = pick(std::integral_constant<int, 4>());
-    }
-    if (rc0) return rc0;
-    k_assign_finalize<<<blocks_for(n), 256, 0, s>>>(n, dim, X, rows, C, keys, labels, sq_dist, stop,
-                                                    step_i);
-    GDD_LAUNCHED();
-    return GDD_OK;
-  }
-  const int waves = dimp16 <= 96 ? 4 : (dimp16 <= 224 ? 2 : 1);
-  const int64_t gx = (n + 32 * waves - 1) / (32 * waves);
-  // centers per block: as many as fit the LDS budget (>= 32), then fewer while the grid is too
-  // small to occupy 256 CUs
-  const size_t budget = dimp16 <= 224 ? 65536 : 160000;
-  const int kp = (k + 31) & ~31;
-  int cch = 32;
-  while (cch + 32 <= kp && assign_lds(waves, dimp16, cch + 32) <= budget) cch += 32;
-  int64_t gy = (k + cch - 1) / cch;
-  while (gx * gy < 1024 && cch > 32) {
-    cch -= 32;
-    gy = (k + cch - 1) / cch;
-  }
-  GDD_REQUIRE(gx < (1ll << 31) && gy < 65536, "assign: grid too large");
-  const size_t lds = assign_lds(waves, dimp16, cch);
-  k_fill_u64<<<blocks_for(n), 256, 0, s>>>(n, keys, ~0ull, stop, step_i);
-  GDD_LAUNCHED();
-  dim3 grid((unsigned)gx, (unsigned)gy);
-  const bool vec = (dim % 4 == 0) &&
-                   ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(C)) & 15) == 0;
-  auto go = [&](auto W_, auto V_) {
-    constexpr int W = decltype(W_)::value;
-    constexpr bool V = decltype(V_)::value;
-    if (lds > 65536)  // gfx950 has 160 KiB of LDS per CU; opt in above the 64 KiB default
-      GDD_HIP(hipFuncSetAttribute((const void*)k_assign<W, V>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-    k_assign<W, V><<<grid, 64 * W, lds, s>>>(n, dim, dimp16, X, rows, k, C, c_norm2, cch, keys, stop,
-                                             step_i);
-    return GDD_OK;
-  };
-  using T4 = std::integral_constant<int, 4>;
-  using T2 = std::integral_constant<int, 2>;
-  using T1 = std::integral_constant<int, 1>;
-  using VT = std::true_type;
-  using VF = std::false_type;
-  int rc0;
-  if (waves == 4)
-    rc0 = vec ? go(T4(), VT()) : go(T4(), VF());
-  else if (waves == 2)
-    rc0 = vec ? go(T2(), VT()) : go(T2(), VF());
-  else
-    rc0 = vec ? go(T1(), VT()) : go(T1(), VF());
-  if (rc0) return rc0;
-  GDD_LAUNCHED();
-  k_assign_finalize<<<blocks_for(n), 256, 0, s>>>(n, dim, X, rows, C, keys, labels, sq_dist, stop,
-                                                  step_i);
-  GDD_LAUNCHED();
-  return GDD_OK;
 }
 }  // namespace
 
@@ -1815,16 +2004,7 @@ int kmeans_assign_dev(int64_t n, int dim, const float* X, int k, const float* C,
 }
 
 // the Lloyd loop's bounded E-step needs the top-2 wave-tile pass with every centre in one chunk
-static int top2_waves(int dim, int k) {
-  const int dimp16 = (dim + 15) & ~15;
-  if (dimp16 > 48) return 0;
-  const int dimpw = (dim + 1) & ~1;
-  for (int wv : {12, 8, 4})
-    if (assign_lds(wv, dimpw, (k + 31) & ~31) <= 150 * 1024) return wv;
-  return 0;
-}
-
-bool lloyd_prune_ok(int dim, int k) { return top2_waves(dim, k) > 0; }
+bool lloyd_prune_ok(int dim, int k) { return assign_plan(1, dim, k, GDD_ASSIGN_TOP2, 0).path == ASSIGN_WAVES; }
 
 // ||C||^2 into cn2, then keys[p] (packed best distance + centre) and sec[p] (second-smallest
 // distance) for rows p < *n_dev (rows[p] with a row list, else p); n_max bounds the grid
@@ -1832,43 +2012,23 @@ int kmeans_assign_top2_dev(int64_t n_max, int dim, const float* X, const int64_t
                            const int64_t* n_dev, int k, const float* C, float* cn2,
                            unsigned long long* keys, float* sec, const int32_t* stop, int step_i,
                            hipStream_t s, const float* Xp, int ldp) {
-  const int Wn = top2_waves(dim, k);
-  GDD_REQUIRE(Wn > 0 && n_max > 0, "assign_top2: unsupported shape");
+  const bool padded = Xp && ldp % 4 == 0 && ldp >= dim && ldp <= 48 && aligned16(Xp);
+  const AssignPlan p = assign_plan(n_max, dim, k, assign_flags(X, C, rows) | GDD_ASSIGN_TOP2 |
+                                                      (padded ? GDD_ASSIGN_PADDED : 0), 0);
+  GDD_REQUIRE(p.path == ASSIGN_WAVES, "assign_top2: unsupported shape");
   k_row_norms<<<blocks_for(k), 256, 0, s>>>(k, dim, C, cn2, stop, step_i);
   GDD_LAUNCHED();
-  const int dimpw = (dim + 1) & ~1;
-  const int cch = (k + 31) & ~31;
-  const size_t lds = assign_lds(Wn, dimpw, cch);
-  const int64_t wtiles = (n_max + 31) / 32;
-  const bool contig = rows == nullptr && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  // a row list over the padded copy: 16-byte pieces of aligned rows (F = 6 pieces per lane cover 48)
-  const bool row4 = !contig && Xp && ldp % 4 == 0 && ldp >= dim && ldp <= 48 &&
-                    (reinterpret_cast<uintptr_t>(Xp) & 15) == 0;
-  auto go = [&](auto kern, int wv) -> int {
-    if (lds > 65536)
-      GDD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int res = 0;
-    const int rrc = resident_blocks((const void*)kern, 64 * wv, lds, &res);
-    if (rrc) return rrc;
-    const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((wtiles + wv - 1) / wv, res));
-    kern<<<dim3((unsigned)gx, 1), 64 * wv, lds, s>>>(n_max, dim, dimpw, row4 ? Xp : X, rows, k, C, cn2, cch,
-                                                     keys, stop, step_i, sec, n_dev, row4 ? ldp : 0);
-    GDD_LAUNCHED();
-    return GDD_OK;
-  };
-  auto pick = [&](auto W_) -> int {
-    constexpr int Wc = decltype(W_)::value;
-    if (contig) return go(k_assign_waves<2, Wc, true, 6, true>, Wc);
-    return row4 ? go(k_assign_waves<2, Wc, false, 6, true, true>, Wc) : go(k_assign_waves<2, Wc, false, 6, true>, Wc);
-  };
-  if (Wn == 12) return pick(std::integral_constant<int, 12>());
-  if (Wn == 8) return pick(std::integral_constant<int, 8>());
-  return pick(std::integral_constant<int, 4>());
+  return assign_waves(p, AssignArgs{n_max, dim, X, rows, k, C, cn2, nullptr, nullptr, keys, stop, step_i, sec,
+                                    n_dev, Xp, ldp}, s);
 }
 }  // namespace gdd
 
 extern "C" size_t gdd_kmeans_assign_ws_bytes(int64_t n) {
   return align256(sizeof(unsigned long long) * (size_t)std::max<int64_t>(n, 1));
+}
+
+extern "C" const char* gdd_kmeans_assign_path(int64_t n, int dim, int k, int flags) {
+  return assign_path_name(assign_plan(n, dim, k, flags, gdd_kmeans_assign_ws_bytes(n)));
 }
 
 extern "C" int gdd_kmeans_assign(int64_t n, int dim, const float* X, const int64_t* rows, int k,
@@ -1892,83 +2052,22 @@ extern "C" int gdd_kmeans_assign_bf16(int64_t n, int dim, const float* X, const 
   if (ws_bytes < gdd_kmeans_assign_ws_bytes(n))
     return fail(GDD_E_WORKSPACE, "kmeans_assign_bf16: workspace too small");
   hipStream_t s = to_hip(stream);
-  float* cn_tmp = nullptr;  // c_norm2 NULL: the r06 pass computes them in its fragment kernel, the
-  auto own_norms = [&]() -> int {  // other forms here, into a stream-ordered temporary
-    if (c_norm2) return GDD_OK;
+  const AssignPlan p = assign_plan(n, dim, k, assign_flags(X, C, rows) | GDD_ASSIGN_BF16, ws_bytes);
+  GDD_REQUIRE(p.path != ASSIGN_INVALID, "kmeans_assign_bf16: grid or LDS too large");
+  float* cn_tmp = nullptr;  // c_norm2 NULL: the r06 pass computes them in its own launch where they fit,
+  if (!c_norm2 && p.need_norms) {  // the other forms here, into a stream-ordered temporary
     GDD_HIP(hipMallocAsync(reinterpret_cast<void**>(&cn_tmp), sizeof(float) * (size_t)k, s));
     k_row_norms<<<blocks_for(k), 256, 0, s>>>(k, dim, C, cn_tmp, nullptr, 0);
     GDD_LAUNCHED();
     c_norm2 = cn_tmp;
-    return GDD_OK;
-  };
-  auto done = [&](int rc) -> int {
-    if (cn_tmp) GDD_HIP(hipFreeAsync(cn_tmp, s));
-    return rc;
-  };
-  unsigned long long* keys = static_cast<unsigned long long*>(ws);
-  const int dimp16 = (dim + 15) & ~15;
-  {  // the persistent kernel: whole rows (no gathered rows), dim <= 128, centre fragments fit LDS
-    const int nsteps = dimp16 / 16, ktiles = (k + 31) / 32;
-    const size_t lds = assign_bf16p_lds(ktiles, nsteps, dim);
-    const int per_need = (8 * dim + 63) / 64;
-    const bool aligned = (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-    const size_t fb = bf16_frag_bytes(ktiles, nsteps);
-    if (!rows && dim <= 128 && aligned && lds <= 150 * 1024 && fb <= ws_bytes) {
-      // the r06 kernel (gdd_bf16.hip) where its shapes allow; GDD_FORCE=bf16_v1: the r03 kernel (A/B)
-      if (!forced("bf16_v1") && n >= 32 && nsteps <= 4 && dim % 16 != 0) {
-        if (!bf16q_norms_fit(dim, k))
-          if (const int rc = own_norms()) return rc;
-        return done(bf16q_launch(n, dim, X, k, C, c_norm2, labels, sq_dist, s));
-      }
-      if (const int rc = own_norms()) return rc;
-      const int64_t ntiles = (n + 31) / 32;
-      bf16x8_t* frags = static_cast<bf16x8_t*>(ws);  // the keys are not used on this path
-      float* cn = reinterpret_cast<float*>(static_cast<char*>(ws) + (size_t)ktiles * nsteps * 64 * 16);
-      const int nfr = std::max(ktiles * nsteps * 64, ktiles * 32);
-      k_bf16_frags<<<(nfr + 255) / 256, 256, 0, s>>>(dim, nsteps, ktiles, k, C, c_norm2, frags, cn);
-      GDD_LAUNCHED();
-      auto go = [&](auto P_) -> int {
-        constexpr int P = decltype(P_)::value;
-        const void* fn = (const void*)k_assign_bf16p<P>;
-        GDD_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int res = 0;
-        const int rrc = resident_blocks(fn, 256, lds, &res);
-        if (rrc) return done(rrc);
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ntiles + 3) / 4, (int64_t)res));
-        k_assign_bf16p<P><<<grid, 256, lds, s>>>(n, dim, nsteps, ktiles, X, k, frags, cn, C, labels, sq_dist);
-        GDD_LAUNCHED();
-        return done(GDD_OK);
-      };
-      if (per_need <= 1) return go(std::integral_constant<int, 1>());
-      if (per_need <= 2) return go(std::integral_constant<int, 2>());
-      if (per_need <= 4) return go(std::integral_constant<int, 4>());
-      if (per_need <= 6) return go(std::integral_constant<int, 6>());
-      if (per_need <= 8) return go(std::integral_constant<int, 8>());
-      if (per_need <= 12) return go(std::integral_constant<int, 12>());
-      return go(std::integral_constant<int, 16>());
-    }
   }
-  constexpr int kWaves = 4;
-  const int64_t gx = (n + 32 * kWaves - 1) / (32 * kWaves);
-  const int kp = (k + 31) & ~31;
-  int cch = 32;
-  while (cch + 32 <= kp && assign_bf16_lds(kWaves, dimp16, cch + 32) <= 65536) cch += 32;
-  int64_t gy = (k + cch - 1) / cch;
-  while (gx * gy < 1024 && cch > 32) {
-    cch -= 32;
-    gy = (k + cch - 1) / cch;
-  }
-  GDD_REQUIRE(gx < (1ll << 31) && gy < 65536, "kmeans_assign_bf16: grid too large");
-  if (const int rc = own_norms()) return rc;
-  const size_t lds = assign_bf16_lds(kWaves, dimp16, cch);
-  k_fill_u64<<<blocks_for(n), 256, 0, s>>>(n, keys, ~0ull, nullptr, 0);
-  GDD_LAUNCHED();
-  k_assign_bf16<kWaves><<<dim3((unsigned)gx, (unsigned)gy), 64 * kWaves, lds, s>>>(
-      n, dim, dimp16, X, rows, k, C, c_norm2, cch, keys);
-  GDD_LAUNCHED();
-  k_assign_finalize<<<blocks_for(n), 256, 0, s>>>(n, dim, X, rows, C, keys, labels, sq_dist, nullptr, 0);
-  GDD_LAUNCHED();
-  return done(GDD_OK);
+  const AssignArgs a{n, dim, X, rows, k, C, c_norm2, labels, sq_dist, static_cast<unsigned long long*>(ws),
+                     nullptr, 0, nullptr, nullptr, nullptr, 0};
+  const int rc = p.path == ASSIGN_BF16Q   ? bf16q_launch(n, dim, X, k, C, c_norm2, labels, sq_dist, p.waves, s)
+                 : p.path == ASSIGN_BF16P ? assign_bf16p(p, a, ws, s)
+                                          : assign_bf16_tiles(p, a, s);
+  if (cn_tmp) GDD_HIP(hipFreeAsync(cn_tmp, s));
+  return rc;
 }
 
 
@@ -1994,9 +2093,7 @@ int launch_update(int64_t b, int dim, const float* X, const int64_t* rows, const
   GDD_REQUIRE(b <= kMaxBatch, "minibatch: batch %lld exceeds %lld", (long long)b,
               (long long)kMaxBatch);
   const size_t lds = update_lds(b);
-  if (lds > 65536)
-    GDD_HIP(hipFuncSetAttribute((const void*)k_minibatch_update,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (const int rc = lds_opt_in((const void*)k_minibatch_update, lds)) return rc;
   k_minibatch_update<<<k, 64, lds, s>>>(b, dim, X, rows, w, labels, keys, k, C_old, C_new, Wsum,
                                         cn2_out, stop, step_i, labels_out, sq_out, keys_reset);
   GDD_LAUNCHED();
@@ -2014,9 +2111,7 @@ int launch_mb_assign_t(int64_t b, int dim, const float* X, const int64_t* rows, 
   const int P = (int)((b + 31) / 32);
   const size_t lds = std::max({mb_assign_lds(W, dim), sizeof(float) * 2048 + 16,
                                kMtRingBytes + 64});
-  if (lds > 65536)
-    GDD_HIP(hipFuncSetAttribute((const void*)k_mb_assign<W, VEC>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (const int rc = lds_opt_in((const void*)k_mb_assign<W, VEC>, lds)) return rc;
   const unsigned grid = (unsigned)(P * G) + (tl.active ? 1u : 0u) + (rn.rows ? 1u : 0u);
   k_mb_assign<W, VEC><<<grid, 64 * W, lds, s>>>(b, dim, dimp, X, rows, k, C, cn2, keys, G, P, stop,
                                                 step_i, tl, rn);
@@ -2479,9 +2574,7 @@ int mb_reassign_launch(int step, int64_t bs, int dim, int k, float ratio, const 
     lds = std::max(lds, par_lds);
   else
     form &= ~kRsParCopy;
-  if (lds > 65536)
-    GDD_HIP(hipFuncSetAttribute((const void*)k_mb_reassign, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
+  if (const int rc = lds_opt_in((const void*)k_mb_reassign, lds)) return rc;
   k_mb_reassign<<<1, 1024, lds, s>>>(step, bs, dim, k, ratio, X, rows, C_new, counts, w.cn2, mt_in,
                                      mt_mid, rn, static_cast<MBState*>(state), form);
   GDD_LAUNCHED();

@@ -105,6 +105,7 @@ SIGNATURES = {
     "gdd_kmeans_plusplus_ws_bytes": (_c_size, [_c_i64, _c_int, _c_int]),
     "gdd_kmeans_plusplus_ws_bytes_k": (_c_size, [_c_i64, _c_int, _c_int, _c_int]),
     "gdd_kmeans_plusplus_path": (ctypes.c_char_p, [_c_i64, _c_int, _c_int, _c_int]),
+    "gdd_kmeans_assign_path": (ctypes.c_char_p, [_c_i64, _c_int, _c_int, _c_int]),
     "gdd_kmeans_plusplus": (_c_int, [_c_i64, _c_int, _vp, _vp, _c_int, _c_int, _c_i64, _vp, _vp,
                                      _vp, _vp, _c_size, _vp]),
     "gdd_standard_scaler": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _vp]),

@@ -161,6 +161,20 @@ int gdd_kmeans_assign(int64_t n, int dim, const float* X, const int64_t* rows, i
 int gdd_kmeans_assign_bf16(int64_t n, int dim, const float* X, const int64_t* rows, int k,
                            const float* C, const float* c_norm2, int32_t* labels, float* sq_dist,
                            void* ws, size_t ws_bytes, gdd_stream_t stream);
+/* the launch path a labels pass takes under the current GDD_FORCE, by name (host only, no device   */
+/* call), for the workspace gdd_kmeans_assign_ws_bytes(n). flags say what the pointers would:        */
+#define GDD_ASSIGN_ROWS 1        /* a row list is given                                              */
+#define GDD_ASSIGN_X_UNALIGNED 2 /* X is not 16-byte aligned                                         */
+#define GDD_ASSIGN_C_UNALIGNED 4 /* C is not 16-byte aligned                                         */
+#define GDD_ASSIGN_BF16 8        /* gdd_kmeans_assign_bf16                                           */
+#define GDD_ASSIGN_TOP2 16       /* the Lloyd loop's bounded E-step (best and second-best distance)  */
+#define GDD_ASSIGN_PADDED 32     /* ... with the zero-padded copy of X offered for its row lists     */
+/* small/w<waves>/vec|scalar, waves[_top2]/w<waves>/contig|rows|row4/<chunk>x<chunks>[/prefill],      */
+/* persist/<chunk>x<chunks>[/prefill], tiles/w<waves>/vec|scalar/<chunk>x<chunks>/prefill,            */
+/* bf16q/w<waves>, bf16p/per<loads>, bf16_tiles/<chunk>x<chunks>/prefill; "invalid" for a shape the   */
+/* entry point refuses (and for n = 0, which launches nothing). The string is the calling thread's    */
+/* until its next call.                                                                               */
+const char* gdd_kmeans_assign_path(int64_t n, int dim, int k, int flags);
 
 /* out[0] = sequential fp32 sum of sq_dist[i] * w[i] in sample order (w == NULL: ones); this is      */
 /* sklearn _inertia_dense with one OpenMP thread (_k_means_common.pyx:92-121).                       */

@@ -65,6 +65,32 @@ def test_assign_large_n_wave_tiles(n, dim, k, mode):
     assert np.array_equal(bits(sq.cpu().numpy()), bits(sq_ref))
 
 
+@pytest.mark.parametrize("n,dim,k,path", [
+    (16385, 64, 100, "persist/128x1"),                  # the persistent form, one chunk, plain stores
+    (16385, 96, 300, "persist/64x5/prefill"),           # ... its widest rows, merged keys
+    (16385, 97, 300, "tiles/w2/scalar/64x5/prefill"),   # k_assign<2, .>: the first dim past the persistent form
+    (16385, 224, 300, "tiles/w2/vec/32x10/prefill"),    # ... its widest rows, float4 loads
+    (16385, 225, 300, "tiles/w1/scalar/128x3/prefill"),  # k_assign<1, .>
+    (16385, 33, 769, "waves/w8/contig/800x1/prefill"),  # 8-wave tiles, every centre in one chunk
+])
+def test_assign_large_n_each_form(n, dim, k, path):
+    """Just past the small-batch limit every other kernel form of the labels pass is the oracle's
+    assignment bit for bit, and the shape takes the form it is meant to pin."""
+    from gdd import _lib
+    assert _lib.device_lib().gdd_kmeans_assign_path(n, dim, k, 0).decode() == path
+    rng = np.random.default_rng(n + k)
+    X = (rng.standard_normal((n, dim)) * 3).astype(np.float32)
+    C = X[rng.choice(n, size=k, replace=False)] + np.float32(0.01)
+    lab_ref, sq_ref = O.assign(X, C)
+    Xd, Cd = torch.from_numpy(X).cuda(), torch.from_numpy(np.ascontiguousarray(C)).cuda()
+    assert Xd.data_ptr() % 16 == 0 and Cd.data_ptr() % 16 == 0  # what the name's flags (none) say
+    lab = torch.empty(n, dtype=torch.int32, device="cuda")
+    sq = torch.empty(n, dtype=torch.float32, device="cuda")
+    _Ops("cuda", n, k, dim).assign(Xd, Cd, labels=lab, sq=sq)
+    assert np.array_equal(lab.cpu().numpy(), lab_ref)
+    assert np.array_equal(bits(sq.cpu().numpy()), bits(sq_ref))
+
+
 def test_assign_ties_between_tiles_and_zero_signs():
     # identical centres in different 32-centre tiles and chunks: the lowest index must win, also
     # when the distance is exactly zero (the packed key treats -0.0 and +0.0 as one value)

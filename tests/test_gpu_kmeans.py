@@ -172,13 +172,20 @@ def test_minibatch_tol_path():
                                           (1000, 47, 1, ""), (40000, 41, 769, ""), (40000, 41, 769, "bf16_w4"),
                                           (9000, 45, 100, "bf16_w8"), (9000, 45, 100, "bf16_v1"),
                                           (3000, 200, 30, ""), (33, 41, 5, ""), (95, 47, 3, ""),
-                                          (64, 45, 40, "bf16_w8")])
+                                          (64, 45, 40, "bf16_w8"), (2048, 47, 1100, ""),
+                                          (2048, 47, 1100, "bf16_w8"), (16000, 47, 1100, ""),
+                                          (16000, 47, 1100, "bf16_w8")])
 def test_assign_bf16_within_rounding(n, dim, k, form, monkeypatch):
     # the bf16 distance variant: labels equal the exact fp32 ones except where two
     # centres' distances lie within the bf16 rounding of the dot products (2^-7 ||x|| ||c|| each).
-    # form: the 4- or 8-wave block form of the r06 kernel, or the r03 kernel (gdd_bf16.hip)
+    # form: the 4- or 8-wave block form of the r06 kernel, or the r03 kernel (gdd_bf16.hip).
+    # 1100 centres of 47: the 8-wave form's LDS does not fit, so the 4-wave form runs, also under
+    # bf16_w8 (n = 16000; at n = 2048 the workspace is too small for either persistent kernel: the tiles)
     from gdd.kmeans import _Ops
     force(monkeypatch, *([form] if form else []))
+    if k == 1100:
+        assert _lib.device_lib().gdd_kmeans_assign_path(n, dim, k, 8).decode() == (
+            "bf16q/w4" if n == 16000 else "bf16_tiles/32x35/prefill")
     rng = np.random.default_rng(n + k)
     X = (rng.standard_normal((n, dim)) + rng.integers(0, 5, (n, 1))).astype(np.float32)
     C = X[rng.choice(n, k, replace=False)] + rng.standard_normal((k, dim)).astype(np.float32) * 0.1
