@@ -23,14 +23,18 @@ than ``(n+m) × d`` or the number of interactions is allocated (the reference ma
   the device (duplicate pairs raise ``ValueError``: the reference would count them twice);
 * :class:`RankformerLayer`, :class:`GCNLayer` (rec.py:92-140);
 * :class:`RankformerTeacher` — model.py:123-250 and the BPR loss of :402-468, with a device negative
-  sampler that redraws until no ``(u, j)`` is a training pair;
+  sampler that redraws until no ``(u, j)`` is a training pair, the contrastive branch (``use_cl``,
+  ``cl_layer``, ``cl_lambda``, ``cl_eps``, ``cl_tau``) and the layer's three ablation switches
+  (``del_neg``, ``del_benchmark``, ``del_omega_norm``);
+* :func:`infonce`, :func:`infonce_rows` — model.py:10-24 as two streaming HIP passes
+  (csrc/gdd_infonce.hip, DESIGN.md "Contrastive loss"): the ``B × B`` logits of the reference are
+  never stored, forward and backward are bit-reproducible;
 * :func:`train_teacher` (main.py:141-190 with parse.py's defaults), :func:`save_teacher`
   (main.py:219-227). The command line is :mod:`gdd.train_teacher`.
 
-Not offered: the contrastive loss (``--use_cl``), the three ablation switches (``--del_neg``,
-``--del_benchmark``, ``--del_omega_norm``), and the reference's random trajectory: the device RNG
-stream differs from the reference's, results are deterministic for a seed on one device. There is no
-CPU path.
+Not offered: the reference's random trajectory: the device RNG stream differs from the reference's,
+results are deterministic for a seed on one device. With ``use_cl`` the reference evaluates the noisy
+embeddings its last training step left behind; here evaluation is noise-free. There is no CPU path.
 
 Validation is Recall@K by :class:`gdd.recsys.RecallEvaluator` by default; ``select_by="ndcg"`` is the
 reference's loop (main.py:100-120): precision, recall and NDCG at ``topks`` by
@@ -147,6 +151,94 @@ def _add(a, b):
     if a is None:
         return b
     return a if b is None else a + b
+
+
+def _check_infonce(a: torch.Tensor, y: torch.Tensor, tau: float) -> Tuple[int, int, float]:
+    if a.dim() != 2 or a.shape != y.shape:
+        raise ValueError("infonce: a and y must be two matrices of one shape")
+    if not float(tau) > 0.0:
+        raise ValueError(f"infonce: tau must be positive, got {tau!r}")
+    return int(a.shape[0]), _check_dim(a.shape[1]), 1.0 / float(tau)
+
+
+def infonce_row_pass(a: torch.Tensor, y: torch.Tensor, tau: float, want_R: bool = True):
+    """``gdd_infonce_rows``: (lse [B], diag [B], pd [B], R [B, d]; pd and R None unless ``want_R``)
+    with ``ℓ_rc = ⟨a_r, y_c⟩ / tau``, ``lse_r = log Σ_c exp ℓ_rc``, ``diag_r = ℓ_rr``,
+    ``pd_r = exp(ℓ_rr − lse_r)``, ``R_r = Σ_c exp(ℓ_rc − lse_r) y_c``. No ``B × B`` object is built."""
+    lib = _lib.device_lib()
+    a, y = _f32(a), _f32(y)
+    B, d, inv_tau = _check_infonce(a, y, tau)
+    dev = a.device
+    lse = torch.empty(B, dtype=torch.float32, device=dev)
+    diag = torch.empty(B, dtype=torch.float32, device=dev)
+    pd = torch.empty(B, dtype=torch.float32, device=dev) if want_R else None
+    R = torch.empty(B, d, dtype=torch.float32, device=dev) if want_R else None
+    ws = _lib.workspace(lib.gdd_infonce_ws_bytes(B, d), dev)
+    _lib.check(lib.gdd_infonce_rows(B, d, a.data_ptr(), y.data_ptr(), inv_tau, lse.data_ptr(), diag.data_ptr(),
+                                    _lib.ptr(pd), _lib.ptr(R), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+    return lse, diag, pd, R
+
+
+def infonce_col_pass(a: torch.Tensor, y: torch.Tensor, tau: float, lse: torch.Tensor, pd: torch.Tensor,
+                     G: torch.Tensor):
+    """``gdd_infonce_cols``: ``C_c = Σ_r G_r exp(ℓ_rc − lse_r) a_r`` [B, d], ``lse`` and ``pd`` from
+    :func:`infonce_row_pass`."""
+    lib = _lib.device_lib()
+    a, y, lse, pd, G = _f32(a), _f32(y), _f32(lse), _f32(pd), _f32(G)
+    B, d, inv_tau = _check_infonce(a, y, tau)
+    if lse.shape != (B,) or pd.shape != (B,) or G.shape != (B,):
+        raise ValueError("infonce_col_pass: lse, pd and G must have one entry per row")
+    dev = a.device
+    C = torch.empty(B, d, dtype=torch.float32, device=dev)
+    ws = _lib.workspace(lib.gdd_infonce_ws_bytes(B, d), dev)
+    _lib.check(lib.gdd_infonce_cols(B, d, a.data_ptr(), y.data_ptr(), inv_tau, lse.data_ptr(), pd.data_ptr(),
+                                    G.data_ptr(), C.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+    return C
+
+
+class _InfoNCERows(torch.autograd.Function):
+    """loss_r = lse_r − ℓ_rr. Backward, with P_rc = exp(ℓ_rc − lse_r) and R_r = Σ_c P_rc y_c saved
+    from the forward: da_r = G_r (R_r − y_r) / tau; dy_c = (Σ_r G_r P_rc a_r − G_c a_c) / tau, the sum
+    being one column pass. Both passes add their diagonal term last (``pd`` = P_rr goes from the row
+    pass to the column pass), so the two subtractions do not keep a long chain's rounding of the part
+    they remove."""
+
+    @staticmethod
+    def forward(ctx, a, y, tau, want):
+        lse, diag, pd, R = infonce_row_pass(a, y, tau, want_R=want)
+        ctx.tau = float(tau)
+        if want:
+            ctx.save_for_backward(a, y, lse, pd, R)
+        return lse - diag
+
+    @staticmethod
+    def backward(ctx, g):
+        a, y, lse, pd, R = ctx.saved_tensors
+        inv_tau = 1.0 / ctx.tau
+        G = _f32(g)
+        Gc = G.unsqueeze(1)
+        da = dy = None
+        if ctx.needs_input_grad[0]:
+            da = (inv_tau * (Gc * (R - y))).to(a.dtype)
+        if ctx.needs_input_grad[1]:
+            dy = (inv_tau * (infonce_col_pass(a, y, ctx.tau, lse, pd, G) - Gc * a)).to(y.dtype)
+        return da, dy, None, None
+
+
+def infonce_rows(a: torch.Tensor, y: torch.Tensor, tau: float) -> torch.Tensor:
+    """The per-row InfoNCE losses ``−log softmax(a yᵀ / tau)_rr`` [B] of two fp32 ``B × d`` matrices
+    (the caller normalises), by two streaming HIP passes (csrc/gdd_infonce.hip): no logit is stored,
+    the forward and the backward give the same bits on every run. Under ``torch.no_grad()``, or when
+    neither input needs a gradient, the backward's ``R`` is not computed."""
+    want = torch.is_grad_enabled() and (a.requires_grad or y.requires_grad)  # ctx cannot tell no_grad
+    return _InfoNCERows.apply(a, y, tau, want)
+
+
+def infonce(x: torch.Tensor, y: torch.Tensor, tau: float = 0.15, b_cos: bool = True) -> torch.Tensor:
+    """model.py:10-24: ``−diag(log_softmax(x̂ ŷᵀ / tau)).mean()``, rows L2-normalised when ``b_cos``."""
+    if b_cos:
+        x, y = F.normalize(x), F.normalize(y)
+    return infonce_rows(x, y, tau).mean()
 
 
 class _RowPass(torch.autograd.Function):
@@ -275,6 +367,22 @@ class InteractionGraph:
         self.dneg = (m - deg_u).clamp(min=1).to(torch.float32).unsqueeze(1)  # d⁻ [n, 1]
         self.train_u = self.users.rows_l  # the pairs in CSR order (int64)
         self.train_i = col.long()
+        self._pair_sets: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+
+    def _pairs(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self._pair_sets is None:  # once per graph: the full-batch contrastive loss asks every epoch
+            self._pair_sets = (torch.unique(self.train_u), torch.unique(self.train_i))
+        return self._pair_sets
+
+    @property
+    def pair_users(self) -> torch.Tensor:
+        """``unique(train_u)``: the users with a training pair, ascending (int64)."""
+        return self._pairs()[0]
+
+    @property
+    def pair_items(self) -> torch.Tensor:
+        """``unique(train_i)``: the items with a training pair, ascending (int64)."""
+        return self._pairs()[1]
 
     def check(self) -> None:
         """Raise if a pass met a column outside its table (one host read)."""
@@ -288,11 +396,21 @@ class InteractionGraph:
 
 class RankformerLayer(nn.Module):
     """rec.py:143-274 in the fused form of the module docstring. ``forward(x, graph)``: x is
-    ``(n+m, d)`` fp32, users first; returns ``cat(z_u, z_i)``."""
+    ``(n+m, d)`` fp32, users first; returns ``cat(z_u, z_i)``.
 
-    def __init__(self, alpha: float = 2.0, clamp_value: float = 0.0):
+    The ablation switches (rec.py:219-221, :263-274) change the algebra around the two row passes,
+    not the passes. ``del_benchmark`` takes ``b⁺ = b⁻ = 0`` in Ω and in the second term of each
+    denominator (the first term of the user denominators, ``b⁺`` resp. ``−b⁻`` itself, stays: the
+    reference recomputes it from the sums). ``del_neg`` drops the negative numerator and denominator.
+    ``del_omega_norm`` returns the numerator undivided. With all three off the layer computes what it
+    always did, bit for bit."""
+
+    def __init__(self, alpha: float = 2.0, clamp_value: float = 0.0, del_neg: bool = False,
+                 del_benchmark: bool = False, del_omega_norm: bool = False):
         super().__init__()
         self.alpha, self.clamp_value = float(alpha), float(clamp_value)
+        self.del_neg, self.del_benchmark = bool(del_neg), bool(del_benchmark)
+        self.del_omega_norm = bool(del_omega_norm)
 
     def forward(self, x: torch.Tensor, graph: InteractionGraph) -> torch.Tensor:
         _check_dim(x.shape[1])
@@ -307,20 +425,32 @@ class RankformerLayer(nn.Module):
         S = S.unsqueeze(1)
         bp = S / dp
         bn = ((xu @ xi.sum(0)).unsqueeze(1) - S) / dn
-        num_u = (A + (al - bn) * SV) / dp + (xu @ (xi.t() @ vi) - A - (bp + al) * (vi.sum(0) - SV)) / dn
-        D = (bp - bn + al).clamp(min=c)
-        z_u = num_u / (D + D)
+        # the benchmarks as Ω and the second half of each denominator see them
+        bpz, bnz = (torch.zeros_like(bp), torch.zeros_like(bn)) if self.del_benchmark else (bp, bn)
+        num_u = (A + (al - bnz) * SV) / dp
+        if not self.del_neg:
+            num_u = num_u + (xu @ (xi.t() @ vi) - A - (bpz + al) * (vi.sum(0) - SV)) / dn
+        if self.del_benchmark:
+            d1, d2 = (bp + al).clamp(min=c), (al - bn).clamp(min=c)
+        else:
+            d1 = d2 = (bp - bn + al).clamp(min=c)
+        den_u = d1 if self.del_neg else d1 + d2
         # the item side: one weight and two scalars per interaction, in the transposed entry order
         ru, pt = graph.users.rows_l, graph.users.to_T
-        op = ((s - bn[:, 0][ru] + al) / dp[:, 0][ru])[pt]
-        om = ((s - bp[:, 0][ru] - al) / dn[:, 0][ru])[pt]
-        Y, ta, tb = _WSum.apply(op - om, vu, op, om, graph.items)
-        xun = xu / dn
-        coef = (bp + al) / dn
-        num_i = Y + xi @ (xun.t() @ vu) - (coef * vu).sum(0)
-        den_i = ta.clamp(min=c) + (-(xi @ xun.sum(0) - coef.sum() - tb)).clamp(min=c)
-        z_i = num_i / den_i.unsqueeze(1)
-        return torch.cat([z_u, z_i], 0)
+        op = ((s - bnz[:, 0][ru] + al) / dp[:, 0][ru])[pt]
+        if self.del_neg:
+            num_i, ta, _ = _WSum.apply(op, vu, op, None, graph.items)
+            den_i = ta.clamp(min=c)
+        else:
+            om = ((s - bpz[:, 0][ru] - al) / dn[:, 0][ru])[pt]
+            Y, ta, tb = _WSum.apply(op - om, vu, op, om, graph.items)
+            xun = xu / dn
+            coef = (bpz + al) / dn
+            num_i = Y + xi @ (xun.t() @ vu) - (coef * vu).sum(0)
+            den_i = ta.clamp(min=c) + (-(xi @ xun.sum(0) - coef.sum() - tb)).clamp(min=c)
+        if self.del_omega_norm:
+            return torch.cat([num_u, num_i], 0)
+        return torch.cat([num_u / den_u, num_i / den_i.unsqueeze(1)], 0)
 
 
 class GCNLayer(nn.Module):
@@ -382,37 +512,68 @@ class NegativeSampler:
 
 
 class RankformerTeacher(nn.Module):
-    """model.py:123-250 without the contrastive branch: embeddings ``normal_(std=0.1)``, optional GCN
-    layers (``gcn_mean`` averages the layer outputs), then ``rankformer_layers`` layers blended with
-    ``rankformer_tau``; the BPR loss of :402-468."""
+    """model.py:123-250: embeddings ``normal_(std=0.1)``, optional GCN layers (``gcn_mean`` averages
+    the layer outputs), then ``rankformer_layers`` layers blended with ``rankformer_tau``; the BPR
+    loss of :402-468, with the contrastive term of :449-465 when ``use_cl``.
+
+    The contrastive branch follows model.py:194-250, quirks included. With ``use_cl`` every GCN
+    layer's output gets ``sign(x) · normalize(rand_like(x)) · cl_eps`` added, and the noisy output is
+    what the next layer and ``gcn_mean`` see. The contrastive view is the output of GCN layer
+    ``cl_layer`` (1-based, noise included, whatever ``gcn_mean``); without GCN layers, or with
+    ``cl_layer`` outside ``1 .. gcn_layers``, it is the raw embedding table. The noise is drawn only
+    in training mode, from a generator seeded from ``seed``, so a seed reproduces a run. The
+    reference's evaluation reuses whatever noisy embeddings the last training step left behind
+    (model.py:279-280); this project evaluates noise-free embeddings instead. :meth:`computer`
+    returns ``(users, items)`` as before and keeps the contrastive view in ``cl_view`` for
+    :meth:`loss_bpr`. ``del_neg`` / ``del_benchmark`` / ``del_omega_norm`` are the layer's ablation
+    switches (:class:`RankformerLayer`)."""
 
     def __init__(self, graph: InteractionGraph, hidden_dim: int = 64, use_gcn: bool = False,
                  gcn_layers: int = 1, gcn_left: float = 1.0, gcn_right: float = 0.0, gcn_mean: bool = False,
                  use_rankformer: bool = True, rankformer_layers: int = 1, rankformer_tau: float = 0.5,
-                 rankformer_alpha: float = 2.0, rankformer_clamp_value: float = 0.0, seed: int = 12345):
+                 rankformer_alpha: float = 2.0, rankformer_clamp_value: float = 0.0, seed: int = 12345,
+                 use_cl: bool = False, cl_layer: int = 1, cl_lambda: float = 0.05, cl_eps: float = 0.1,
+                 cl_tau: float = 0.15, del_neg: bool = False, del_benchmark: bool = False,
+                 del_omega_norm: bool = False):
         super().__init__()
         self.graph = graph
         self.hidden_dim = _check_dim(hidden_dim)
         self.use_gcn, self.gcn_layers, self.gcn_mean = bool(use_gcn), int(gcn_layers), bool(gcn_mean)
         self.use_rankformer, self.rankformer_layers = bool(use_rankformer), int(rankformer_layers)
         self.rankformer_tau = float(rankformer_tau)
+        self.use_cl, self.cl_layer = bool(use_cl), int(cl_layer)
+        self.cl_lambda, self.cl_eps, self.cl_tau = float(cl_lambda), float(cl_eps), float(cl_tau)
+        if self.use_cl and not self.cl_tau > 0.0:
+            raise ValueError(f"RankformerTeacher: cl_tau must be positive, got {cl_tau!r}")
         self.embedding_user = nn.Embedding(graph.n, self.hidden_dim)
         self.embedding_item = nn.Embedding(graph.m, self.hidden_dim)
         nn.init.normal_(self.embedding_user.weight, std=0.1)
         nn.init.normal_(self.embedding_item.weight, std=0.1)
         self.GCN = GCNLayer(gcn_left, gcn_right)
-        self.Rankformer = RankformerLayer(rankformer_alpha, rankformer_clamp_value)
+        self.Rankformer = RankformerLayer(rankformer_alpha, rankformer_clamp_value, del_neg, del_benchmark,
+                                          del_omega_norm)
         self.to(graph.device)
         self.sampler = NegativeSampler(graph, seed)
+        self.noise_gen = torch.Generator(device=graph.device)  # its own stream: the sampler's is untouched
+        self.noise_gen.manual_seed(int(seed) + 2)
+        self.cl_view: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
 
     def computer(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The propagated (user, item) embeddings (model.py:166-250)."""
+        """The propagated (user, item) embeddings (model.py:166-250). With ``use_cl`` the contrastive
+        view of the same pass is left in ``cl_view``."""
         g = self.graph
         x = torch.cat([self.embedding_user.weight, self.embedding_item.weight], 0)
+        x_cl = x
+        noisy = self.use_cl and self.training
         if self.use_gcn:
             outs = [x]
-            for _ in range(self.gcn_layers):
+            for layer in range(self.gcn_layers):
                 x = self.GCN(x, g)
+                if noisy:
+                    r = torch.rand(x.shape, generator=self.noise_gen, dtype=x.dtype, device=x.device)
+                    x = x + torch.sign(x) * F.normalize(r, dim=-1) * self.cl_eps
+                if layer == self.cl_layer - 1:
+                    x_cl = x
                 outs.append(x)
             if self.gcn_mean:
                 x = torch.stack(outs, dim=-1).mean(dim=-1)
@@ -420,11 +581,15 @@ class RankformerTeacher(nn.Module):
             tau = self.rankformer_tau
             for _ in range(self.rankformer_layers):
                 x = (1 - tau) * x + tau * self.Rankformer(x, g)
+        self.cl_view = (x_cl[:g.n], x_cl[g.n:]) if self.use_cl else None
         return x[:g.n], x[g.n:]
 
     def loss_bpr(self, users: torch.Tensor, items: torch.Tensor, u: torch.Tensor, i: torch.Tensor,
                  reg_lambda: float = 1e-4, j: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """softplus(s_uj − s_ui).mean() + reg_lambda · ½(‖u₀‖² + ‖i₀‖² + ‖j₀‖²)/B (model.py:402-468)."""
+        """softplus(s_uj − s_ui).mean() + reg_lambda · ½(‖u₀‖² + ‖i₀‖² + ‖j₀‖²)/B (model.py:402-468);
+        with ``use_cl`` plus ``cl_lambda · (infonce(users[uu], users_cl[uu]) + infonce(items[ii],
+        items_cl[ii]))`` over ``uu = unique(u)``, ``ii = unique(i)`` and the contrastive view the
+        last :meth:`computer` left (:449-465)."""
         if j is None:
             j = self.sampler(u)
         u0, i0, j0 = self.embedding_user(u), self.embedding_item(i), self.embedding_item(j)
@@ -432,7 +597,18 @@ class RankformerTeacher(nn.Module):
         s_ui = (ue * items[i]).sum(-1)
         s_uj = (ue * items[j]).sum(-1)
         reg = 0.5 * (u0.norm(2).pow(2) + i0.norm(2).pow(2) + j0.norm(2).pow(2)) / u.shape[0]
-        return F.softplus(s_uj - s_ui).mean() + reg_lambda * reg
+        if not self.use_cl:
+            return F.softplus(s_uj - s_ui).mean() + reg_lambda * reg
+        if self.cl_view is None:
+            raise RuntimeError("RankformerTeacher.loss_bpr: use_cl needs the contrastive view of computer()")
+        users_cl, items_cl = self.cl_view
+        g = self.graph
+        if u is g.train_u and i is g.train_i:  # full batch: the same two sets every epoch
+            uu, ii = g.pair_users, g.pair_items
+        else:
+            uu, ii = torch.unique(u), torch.unique(i)
+        cl = infonce(users[uu], users_cl[uu], self.cl_tau) + infonce(items[ii], items_cl[ii], self.cl_tau)
+        return F.softplus(s_uj - s_ui).mean() + reg_lambda * reg + self.cl_lambda * cl
 
 
 def train_teacher(num_users: int, num_items: int, train_u, train_i, valid_u, valid_i, *,

@@ -7,7 +7,8 @@
 Flags keep the reference's names and defaults where the reference has them (``--hidden_dim``,
 ``--use_gcn``, ``--gcn_layers``, ``--gcn_left``, ``--gcn_right``, ``--gcn_mean``,
 ``--rankformer_layers``, ``--rankformer_tau``, ``--rankformer_alpha``, ``--rankformer_clamp_value``,
-``--learning_rate``, ``--reg_lambda``, ``--loss_batch_size``, ``--max_epochs``, ``--valid_interval``,
+``--use_cl``, ``--cl_layer``, ``--cl_lambda``, ``--cl_eps``, ``--cl_tau``, ``--del_neg``,
+``--del_benchmark``, ``--del_omega_norm``, ``--learning_rate``, ``--reg_lambda``, ``--loss_batch_size``, ``--max_epochs``, ``--valid_interval``,
 ``--stopping_step``, ``--seed``). The Rankformer layers are on unless ``--no_rankformer`` is given
 (``--use_rankformer`` is accepted and changes nothing); ``--data_dir`` / ``--dataset`` are
 ``gdd.distill_recsys``'s. Repeated lines of ``train.txt`` are dropped with a note (the layer is
@@ -50,6 +51,14 @@ def parse_args(argv=None):
     p.add_argument("--rankformer_tau", type=float, default=0.5)
     p.add_argument("--rankformer_alpha", type=float, default=2.0)
     p.add_argument("--rankformer_clamp_value", type=float, default=0.0)
+    p.add_argument("--use_cl", action="store_true", help="add the contrastive (InfoNCE) loss")
+    p.add_argument("--cl_layer", type=int, default=1, help="the GCN layer (1-based) whose output is the view")
+    p.add_argument("--cl_lambda", type=float, default=0.05)
+    p.add_argument("--cl_eps", type=float, default=0.1, help="norm of the noise added after each GCN layer")
+    p.add_argument("--cl_tau", type=float, default=0.15)
+    p.add_argument("--del_neg", action="store_true", help="ablation: no negative pairs in the layer")
+    p.add_argument("--del_benchmark", action="store_true", help="ablation: no benchmark terms in the layer")
+    p.add_argument("--del_omega_norm", action="store_true", help="ablation: the layer's numerator, undivided")
     p.add_argument("--learning_rate", type=float, default=1e-1)
     p.add_argument("--reg_lambda", type=float, default=1e-4)
     p.add_argument("--loss_batch_size", type=int, default=0, help="0: full batch")
@@ -88,7 +97,9 @@ def run(args):
         use_gcn=args.use_gcn, gcn_layers=args.gcn_layers, gcn_left=args.gcn_left, gcn_right=args.gcn_right,
         gcn_mean=args.gcn_mean, use_rankformer=not args.no_rankformer, rankformer_layers=args.rankformer_layers,
         rankformer_tau=args.rankformer_tau, rankformer_alpha=args.rankformer_alpha,
-        rankformer_clamp_value=args.rankformer_clamp_value)
+        rankformer_clamp_value=args.rankformer_clamp_value, use_cl=args.use_cl, cl_layer=args.cl_layer,
+        cl_lambda=args.cl_lambda, cl_eps=args.cl_eps, cl_tau=args.cl_tau, del_neg=args.del_neg,
+        del_benchmark=args.del_benchmark, del_omega_norm=args.del_omega_norm)
     torch.cuda.synchronize()
     if args.select_by == "ndcg":
         print(f"[teacher] {len(hist['loss'])} epochs in {time.perf_counter() - t0:.1f} s; best epoch "

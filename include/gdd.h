@@ -660,6 +660,34 @@ int gdd_rank_metrics(int64_t B, int K, const int32_t* top_item, const int32_t* t
                      const int32_t* te_deg, int nk, const int32_t* topks, const double* inv_log2,
                      double* per_user, double* sums, int64_t* count, gdd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------- */
+/* The teacher's contrastive loss (Rankformer/code/model.py:10-24 InfoNCE, :449-465 its use in the   */
+/* loss; DESIGN.md "Contrastive loss"). A, Y: B x d fp32 row-major (the caller normalises; unit rows */
+/* are not assumed), 1 <= d <= gdd_rank_max_dim(), 0 <= B < 2^31 (B == 0 returns without a launch),  */
+/* inv_tau = 1/tau > 0. l_rc = inv_tau <A_r, Y_c>, the fp32 fmaf chain over f = 0 .. d-1 from +0     */
+/* (f32-input MFMA), the same bits in both passes. No logit is stored: Y (A) streams through the LDS */
+/* in tiles of 32 rows in ascending order. No floating-point atomics, a fixed order for every sum:   */
+/* two runs give the same bits.                                                                      */
+/* gdd_infonce_ws_bytes (model.py:10-24, :449-465): the workspace both passes ask for; 0 (the        */
+/*   columns are not split over workgroups, so there is nothing to merge).                           */
+/* gdd_infonce_rows (model.py:10-24, :449-465): lse[r] = log sum_c exp(l_rc) by online softmax,      */
+/*   diag[r] = l_rr (the row's loss is lse[r] - diag[r]), pd[r] (nullable unless R is given) =       */
+/*   P_rr = exp(l_rr - lse[r]) taken from the running sums, and with R non-null                      */
+/*   R[r] = sum_c exp(l_rc - lse[r]) Y_c (B x d), which the backward needs:                          */
+/*   dA_r = inv_tau G_r (R_r - Y_r). The diagonal term P_rr Y_r is added last, so that this          */
+/*   difference does not carry the large term's rounding through the chain.                          */
+/* gdd_infonce_cols (model.py:10-24, :449-465; the backward of the log-softmax there): with lse and  */
+/*   pd from gdd_infonce_rows and an upstream per-row gradient G [B],                                */
+/*   C[c] = sum_r G_r exp(l_rc - lse[r]) A_r (B x d): dY_c = inv_tau (C_c - G_c A_c). The diagonal   */
+/*   term is G_c pd[c] A_c, added last (the fp32 lse alone gives P_cc only to u |lse|).              */
+/* ---------------------------------------------------------------------------------------------- */
+size_t gdd_infonce_ws_bytes(int64_t B, int d);
+int gdd_infonce_rows(int64_t B, int d, const float* A, const float* Y, float inv_tau, float* lse,
+                     float* diag, float* pd, float* R, void* ws, size_t ws_bytes, gdd_stream_t stream);
+int gdd_infonce_cols(int64_t B, int d, const float* A, const float* Y, float inv_tau, const float* lse,
+                     const float* pd, const float* G, float* C, void* ws, size_t ws_bytes,
+                     gdd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
