@@ -24,9 +24,11 @@
 //     larger index adds magnitude, the lower index wins a tie), and a balanced v_min3_i32 tree takes
 //     the tile's 16 keys per lane (8 per centre tile) — per centre 1.5 VALU, where the r03 epilogue
 //     spent an fma, a compare and two selects (plus a copy out of the accumulator).
-// Accuracy: the labels are those of bf16 dot products (tests/test_gpu_kmeans.py and
-// tests/test_gpu_configs.py bound every label that differs from the exact fp32 one by the bf16
-// rounding, 2^-7 ||x|| ||c|| per product). delta = 2^-5 ||x||^2 + 2^-100 keeps acc strictly negative:
+// Accuracy: the labels are those of bf16 dot products: tests/test_gpu_bf16_labels.py requires every
+// label to be the nearest centre under exact bf16-rounded products up to the fp32 accumulation
+// (tests/bf16_model.py), at every instantiation below; tests/test_gpu_kmeans.py and
+// tests/test_gpu_configs.py also bound every label that differs from the exact fp32 one by the bf16
+// rounding, 2^-7 ||x|| ||c|| per product. delta = 2^-5 ||x||^2 + 2^-100 keeps acc strictly negative:
 // a centre whose acc crossed zero would need d / 2 < 2^-7 ||x|| ||c|| + 2^-7 ||x||^2 (the products'
 // rounding; the shift's: ||x||^2 summed from the bf16-rounded features, <= 2^-8 ||x||^2 off, then
 // rounded to bf16) - delta, impossible for ||c|| <= 2.9 ||x|| (the right side is negative) and for

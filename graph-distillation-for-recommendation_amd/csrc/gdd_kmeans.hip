@@ -1745,6 +1745,9 @@ AssignPlan assign_plan(int64_t n, int dim, int k, int flags, size_t ws_bytes) {
       return p;
     }
     p.dimp = dimp16;
+    // dims 497 .. 512: one 32-centre chunk and four waves' points are 166,544 bytes, past a CU's LDS;
+    // two waves per block hold them (99,984)
+    if (assign_bf16_lds(4, dimp16, 32) > kLdsCap) p.waves = 2;
     if (plan_tiles(p, n, k, kTilesLdsBudget, assign_bf16_lds)) p.path = ASSIGN_BF16_TILES;
     return p;
   }
@@ -1970,10 +1973,14 @@ int assign_bf16p(const AssignPlan& p, const AssignArgs& a, void* ws, hipStream_t
 
 int assign_bf16_tiles(const AssignPlan& p, const AssignArgs& a, hipStream_t s) {
   if (const int rc = assign_prefill(p, a, s)) return rc;
-  k_assign_bf16<4><<<dim3((unsigned)p.gx, (unsigned)p.gy), 64 * 4, p.lds, s>>>(a.n, a.dim, p.dimp, a.X, a.rows,
-                                                                             a.k, a.C, a.cn2, p.cch, a.keys);
-  GDD_LAUNCHED();
-  return assign_finalize(a, s);
+  auto go = [&](auto kern) -> int {
+    kern<<<dim3((unsigned)p.gx, (unsigned)p.gy), 64 * p.waves, p.lds, s>>>(a.n, a.dim, p.dimp, a.X, a.rows, a.k,
+                                                                          a.C, a.cn2, p.cch, a.keys);
+    GDD_LAUNCHED();
+    return GDD_OK;
+  };
+  const int rc = p.waves == 2 ? go(k_assign_bf16<2>) : go(k_assign_bf16<4>);
+  return rc ? rc : assign_finalize(a, s);
 }
 
 // labels (+ optional per-sample sq_dist) of n samples against k centres.

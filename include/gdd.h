@@ -155,9 +155,15 @@ int gdd_kmeans_assign(int64_t n, int dim, const float* X, const int64_t* rows, i
 /* bf16 distance variant (configs 2, 3, 5 carry fp32 and bf16 distances). Same        */
 /* arguments and outputs; the X and C operands are rounded to bf16 (nearest even) and the dot       */
 /* products run as v_mfma_f32_32x32x16_bf16 chains with fp32 accumulation; distances use the fp32    */
-/* c_norm2 (NULL: computed on the device, no separate launch on the common shapes). NOT bit-compatible with sklearn: a label may differ where two centres' distances lie     */
-/* within the bf16 rounding of the dot products (|err| <= ~2^-7 ||x|| ||c||). sq_dist is the exact   */
-/* fp32 distance to the chosen centre.                                                              */
+/* c_norm2 (NULL: computed on the device, no separate launch on the common shapes).                  */
+/* Guaranteed: labels[i] is the nearest centre under exact products of the bf16-rounded operands     */
+/* with the fp32 c_norm2, i.e. it minimises c_norm2[j] / 2 - sum_t bf16(X[i,t]) bf16(C[j,t]), up to   */
+/* the fp32 accumulation (~2^-17 of the terms' magnitudes; tests/bf16_model.py derives the bound,     */
+/* tests/test_gpu_bf16_labels.py checks it on every kernel form). Where centres tie within that, the  */
+/* r03 and tiles forms return the first, the r06 form any of them. NOT bit-compatible with sklearn:   */
+/* the distance to the fp32 answer is the operands' rounding, a label may differ where two centres'   */
+/* fp32 distances lie within ~2^-7 ||x|| ||c|| of each other. sq_dist is the exact fp32 distance      */
+/* (_euclidean_dense_dense order) to the chosen centre. dim <= 512 (497 .. 512: two-wave blocks).     */
 int gdd_kmeans_assign_bf16(int64_t n, int dim, const float* X, const int64_t* rows, int k,
                            const float* C, const float* c_norm2, int32_t* labels, float* sq_dist,
                            void* ws, size_t ws_bytes, gdd_stream_t stream);

@@ -104,6 +104,12 @@ PATHS = [
     # persistent kernels as it did before the plan: the tiles
     (2048, 47, 1100, BF16, "", "bf16_tiles/32x35/prefill"),
     (2048, 47, 1100, BF16, "bf16_w8", "bf16_tiles/32x35/prefill"),
+    # the widest dims gdd.h admits: from 497 the four-wave block's LDS (166,544 bytes) is past a CU's,
+    # two waves per block hold it (these were "invalid" before; tests/test_gpu_bf16_labels.py runs them)
+    (2013, 496, 96, BF16, "", "bf16_tiles/32x3/prefill"),
+    (2013, 497, 96, BF16, "", "bf16_tiles/32x3/prefill"),
+    (2013, 512, 96, BF16, "", "bf16_tiles/32x3/prefill"),
+    (1, 512, 1, BF16, "", "bf16_tiles/32x1/prefill"),
 ]
 
 

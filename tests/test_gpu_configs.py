@@ -19,6 +19,7 @@ import scipy.sparse as sp
 import torch
 
 from golden_util import bits, load, load_json
+from gpu_util import bf16_check
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -68,6 +69,10 @@ def test_products_shape_bf16_assignment_within_rounding():
         di = ((X64[i] - C64) ** 2).sum(-1)
         bound = 2 * 2.0 ** -7 * np.linalg.norm(X64[i]) * (cn[a[i]] + cn[b[i]]) + 1e-3 * (1 + di[a[i]])
         assert di[b[i]] - di[a[i]] <= bound
+    # every label the nearest under exact bf16-rounded products up to the fp32 accumulation
+    # (tests/bf16_model.py, which walks the rows in chunks)
+    path = _lib.device_lib().gdd_kmeans_assign_path(n, dim, k, 8).decode()
+    assert path == "bf16q/w4" and bf16_check(X, C, b, path)[0] == 0
     # the exact labels themselves equal the oracle's on a sample of rows
     rows = rng.integers(0, n, 20000)
     lab_ref, _ = O.assign(X[rows], C)

@@ -11,13 +11,7 @@ import gdd  # noqa: E402
 from gdd import _lib, synth  # noqa: E402
 from gdd.kmeans import _Ops  # noqa: E402
 
-
-def force(monkeypatch, *tokens):
-    """GDD_FORCE (gdd_common.hpp): force the listed paths for the next calls (none: the defaults)."""
-    if tokens:
-        monkeypatch.setenv("GDD_FORCE", ",".join(tokens))
-    else:
-        monkeypatch.delenv("GDD_FORCE", raising=False)
+from gpu_util import bf16_check, force  # noqa: E402
 
 
 def bits(a):
@@ -208,6 +202,10 @@ def test_assign_bf16_within_rounding(n, dim, k, form, monkeypatch):
         di = ((X64[i] - C64) ** 2).sum(-1)
         bound = 2 * 2.0 ** -7 * xn[i] * (cn[a[i]] + cn[b[i]]) + 1e-3 * (1 + di[a[i]])
         assert di[b[i]] - di[a[i]] <= bound
+    # that bound is the distance to the fp32 answer; what the kernel guarantees is ~200 times tighter:
+    # the nearest centre under exact bf16-rounded products, up to the fp32 accumulation
+    path = _lib.device_lib().gdd_kmeans_assign_path(n, dim, k, 8).decode()
+    assert bf16_check(X, C, b, path)[0] == 0, path
     # sq_dist is the exact fp32 distance to the chosen centre (the fp32 finalize path)
     i = rng.integers(0, n, 64)
     ref = ((X[i] - C[b[i]]) ** 2).sum(-1)
@@ -599,9 +597,15 @@ def test_assign_bf16_gathered_rows_unaligned_and_predict():
         for i in np.nonzero(a != b)[0][:2000]:
             di = ((X64[i] - C64) ** 2).sum(-1)
             assert di[b[i]] - di[a[i]] <= 2 * 2.0 ** -7 * xn[i] * (cn[a[i]] + cn[b[i]]) + 1e-3 * (1 + di[a[i]]), name
+        # the exact-product model (tests/bf16_model.py): flags 1 = a row list, 2 = X unaligned
+        path = ops.lib.gdd_kmeans_assign_path(n, dim, k, 8 | (1 if name == "rows" else 2)).decode()
+        assert path.startswith("bf16_tiles/"), path
+        assert bf16_check(Xall[1:], C, b, path)[0] == 0, name
     km = gdd.KMeans(n_clusters=k)
     km.cluster_centers_ = C
     p = km.predict(Xall[1:], precision="bf16")
+    path = ops.lib.gdd_kmeans_assign_path(n, dim, k, 8).decode()  # predict copies X: aligned
+    assert path == "bf16q/w4" and bf16_check(Xall[1:], C, p, path)[0] == 0
     for i in np.nonzero(a != p)[0][:2000]:
         di = ((X64[i] - C64) ** 2).sum(-1)
         assert di[p[i]] - di[a[i]] <= 2 * 2.0 ** -7 * xn[i] * (cn[a[i]] + cn[p[i]]) + 1e-3 * (1 + di[a[i]])
