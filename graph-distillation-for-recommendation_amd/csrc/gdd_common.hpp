@@ -72,6 +72,9 @@ size_t sort_pairs_ws_bytes(int64_t n);
 int sort_pairs_i32(const int32_t* keys_in, int32_t* keys_out, const int32_t* vals_in,
                    int32_t* vals_out, int64_t n, int end_bit, void* ws, size_t ws_bytes,
                    hipStream_t s);
+// the same over all 32 bits with the keys compared as unsigned (negative keys last)
+int sort_pairs_u32(const int32_t* keys_in, int32_t* keys_out, const int32_t* vals_in,
+                   int32_t* vals_out, int64_t n, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // launch-sequence replay (hipGraph). A fixed sequence of dependent launches — the k-means++ round
@@ -106,7 +109,9 @@ bool bf16q_norms_fit(int dim, int k);
 // GDD_FORCE=kpp_no_table,lloyd_no_prune or GDD_FORCE=kpp_big1_max=32768. Read on every call (host).
 // The kpp_* tokens are read in one place, kpp_plan (gdd_kmeanspp.hip), which turns them into the
 // launch path that gdd_kmeans_plusplus_path names; the bf16_* tokens likewise in assign_plan
-// (gdd_kmeans.hip) and gdd_kmeans_assign_path.
+// (gdd_kmeans.hip) and gdd_kmeans_assign_path. The Lloyd loop's (gdd_lloyd.hip) are each read in one
+// place too: group_split in group_plan (gdd_group_path), fold_slice in fold_big_rows (gdd_fold_path),
+// lloyd_no_prune in lloyd_bounded, fold_no_pad and estep_no_pad in gdd_kmeans_lloyd_run.
 //   kpp_no_table      k-means++ without the n x n distance table (small and multi-block plans)
 //   kpp_force_table   the multi-block table although kpp_table_pays says no (small k)
 //   kpp_no_big1       the per-block table rounds instead of one workgroup per trial (n <= 16,384)

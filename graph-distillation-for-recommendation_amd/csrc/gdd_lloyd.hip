@@ -38,17 +38,52 @@ inline unsigned blocks_of(int64_t n, int t = 256) { return (unsigned)((n + t - 1
 constexpr int kTileUnit = 1024;   // labels per wave per tile unit (16 per lane)
 constexpr int kCountMaxK = 32768;  // LDS: (waves per block) x k int32 counters
 
+// the one-workgroup form's block (k_grp_small below) and the shapes it takes
+constexpr int kGrpThr = 1024;
+constexpr int kGrpWaves = kGrpThr / 64;
+constexpr int64_t kGrpSmallMaxN = (int64_t)kGrpWaves * 2 * kTileUnit;  // M <= 2
+constexpr int kGrpSmallMaxK = 2 * kGrpThr;
+
+// Which form a grouping takes and its launch geometry; host only, decided once per call.
+enum GroupForm { GROUP_INVALID, GROUP_SMALL, GROUP_COUNT, GROUP_RADIX };
 struct GroupPlan {
+  GroupForm form;  // invalid: the counting form with k x tiles past int32 indexing
   int m;           // tile = m * 1024 labels, one wave each
-  int64_t ntiles;  // columns of the cluster-major histogram matrix
-  int waves;       // waves per 256-lane block (each has its own k counters in LDS)
+  int waves;       // waves per block (each has its own k counters in LDS)
+  int bits;        // label bits (the scatter's ballot match)
+  int64_t ntiles;  // count: columns of the cluster-major histogram matrix
+  unsigned grid;
+  size_t lds;
 };
 
+// the counting form's tile units per wave, and its tiles
+int group_tile_units(int64_t n) { return (int)std::min<int64_t>(4, std::max<int64_t>(1, (n + (1 << 20) - 1) >> 20)); }
+int64_t group_tiles(int64_t n, int m) {
+  return std::max<int64_t>(1, (n + (int64_t)m * kTileUnit - 1) / ((int64_t)m * kTileUnit));
+}
+// elements of each workspace array: the histogram matrix (a small shape's too: group_split counts it) or the rows
+int64_t group_cells(int64_t n, int k) {
+  return k > kCountMaxK ? n : (int64_t)k * group_tiles(n, group_tile_units(n));
+}
+
 GroupPlan group_plan(int64_t n, int k) {
-  GroupPlan p;
-  p.m = (int)std::min<int64_t>(4, std::max<int64_t>(1, (n + (1 << 20) - 1) >> 20));
-  p.ntiles = std::max<int64_t>(1, (n + (int64_t)p.m * kTileUnit - 1) / ((int64_t)p.m * kTileUnit));
-  p.waves = k <= 4096 ? 4 : 1;
+  GroupPlan p{};
+  p.form = GROUP_RADIX;  // k > kCountMaxK: a stable sort of (label, index)
+  for (p.bits = 1; (1ll << p.bits) < (long long)k;) ++p.bits;
+  if (k > kCountMaxK) return p;
+  if (n <= kGrpSmallMaxN && k <= kGrpSmallMaxK && !forced("group_split")) {
+    p.form = GROUP_SMALL;  // one workgroup, one launch, no workspace
+    p.m = n <= (int64_t)kGrpWaves * kTileUnit ? 1 : 2;
+    p.waves = kGrpWaves;
+    p.grid = 1;
+  } else {  // histograms, scan, scatter
+    p.m = group_tile_units(n);
+    p.ntiles = group_tiles(n, p.m);
+    p.form = (int64_t)k * p.ntiles < INT_MAX ? GROUP_COUNT : GROUP_INVALID;
+    p.waves = k <= 4096 ? 4 : 1;
+    p.grid = (unsigned)((p.ntiles + p.waves - 1) / p.waves);
+  }
+  p.lds = sizeof(int32_t) * (size_t)p.waves * k;
   return p;
 }
 
@@ -140,11 +175,6 @@ __global__ __launch_bounds__(256) void k_grp_scatter(int64_t n, const int32_t* _
 // LDS. Then thread t owns clusters 2t and 2t+1: each column's exclusive prefix over the waves, the
 // block's exclusive scan of the cluster totals, and the tile offsets; then the scatter of
 // k_grp_scatter. Tiles, chunks and lanes are taken in index order: the same stable permutation.
-constexpr int kGrpThr = 1024;
-constexpr int kGrpWaves = kGrpThr / 64;
-constexpr int64_t kGrpSmallMaxN = (int64_t)kGrpWaves * 2 * kTileUnit;  // M <= 2
-constexpr int kGrpSmallMaxK = 2 * kGrpThr;
-
 template <int M>
 __global__ __launch_bounds__(kGrpThr) void k_grp_small(int64_t n, const int32_t* __restrict__ labels, int k,
                                                        int bits, int32_t* __restrict__ perm,
@@ -221,7 +251,8 @@ __global__ __launch_bounds__(kGrpThr) void k_grp_small(int64_t n, const int32_t*
   }
 }
 
-// radix fallback (k > kCountMaxK): stable sort of (label, index), then first-position offsets
+// radix fallback (k > kCountMaxK): stable sort of (label, index), the labels compared as unsigned 32-bit keys so
+// that those outside [0, k) sort behind the clusters', then first-position offsets over the keys clamped to k
 __global__ void k_iota(int64_t n, int32_t* p) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = (int32_t)i;
@@ -231,9 +262,10 @@ __global__ void k_offsets(int64_t n, const int32_t* __restrict__ skeys, int k,
                           int32_t* __restrict__ offsets) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i > n) return;
-  const int prev = (i == 0) ? -1 : skeys[i - 1];
-  const int cur = (i == n) ? k : skeys[i];
-  for (int c = prev + 1; c <= cur && c <= k; ++c) offsets[c] = (int32_t)i;
+  auto key = [&](int64_t j) { return (int64_t)min((uint32_t)skeys[j], (uint32_t)k); };
+  const int64_t lo = (i == 0) ? 0 : key(i - 1) + 1;
+  const int64_t hi = (i == n) ? k : key(i);
+  for (int64_t c = lo; c <= hi; ++c) offsets[c] = (int32_t)i;
 }
 
 // group_dev's buffers beyond the one-launch form (which needs none)
@@ -241,99 +273,65 @@ struct GroupWs {
   int32_t *a, *b;  // counting: the histogram matrix and its scan; radix: the row ids and the sorted keys
   size_t sb;       // the scan's / the sort's own workspace
   void* sws;
+  size_t bytes;    // all of them
 };
 
-// the counting form's buffers for a histogram matrix of `cells`
-void carve_count(Carver& cv, int64_t cells, GroupWs* g) {
-  g->a = cv.take<int32_t>(cells);
-  g->b = cv.take<int32_t>(cells);
-  g->sb = scan_i32_ws_bytes(cells);
-  g->sws = cv.take<char>(g->sb);
-}
-
-// carves them from ws (a null ws: measures) and returns the bytes they take
-size_t carve_group(void* ws, int64_t n, int k, GroupWs* g) {
+// carved from ws (a null ws: measured)
+GroupWs carve_group(void* ws, bool radix, int64_t cells) {
   Carver cv(ws, 0);
-  if (k <= kCountMaxK) {
-    carve_count(cv, (int64_t)k * group_plan(n, k).ntiles, g);
-  } else {
-    g->a = cv.take<int32_t>(n);
-    g->b = cv.take<int32_t>(n);
-    g->sb = sort_pairs_ws_bytes(n);
-    g->sws = cv.take<char>(g->sb);
-  }
-  return cv.off;
+  GroupWs g{cv.take<int32_t>(cells), cv.take<int32_t>(cells)};
+  g.sb = radix ? sort_pairs_ws_bytes(cells) : scan_i32_ws_bytes(cells);
+  g.sws = cv.take<char>(g.sb);
+  g.bytes = cv.off;
+  return g;
 }
 
-size_t group_ws(int64_t n, int k) {
-  GroupWs g;
-  return carve_group(nullptr, n, k, &g) + (k <= kCountMaxK ? 256 : 1024);
-}
+size_t group_ws(bool radix, int64_t cells) { return carve_group(nullptr, radix, cells).bytes + (radix ? 1024 : 256); }
+size_t group_ws(int64_t n, int k) { return group_ws(k > kCountMaxK, group_cells(n, k)); }
 
+// plan, carve, one launcher per form
 int group_dev(int64_t n, const int32_t* labels, int k, int32_t* perm, int32_t* offsets, void* ws,
               size_t ws_bytes, const int32_t* stop, int step_i, hipStream_t s) {
-  if (n <= kGrpSmallMaxN && k <= kGrpSmallMaxK && !forced("group_split")) {
-    int bits = 1;
-    while ((1ll << bits) < (long long)k) ++bits;
-    const size_t lds = sizeof(int32_t) * (size_t)kGrpWaves * k;
-    auto fn = n <= (int64_t)kGrpWaves * kTileUnit ? k_grp_small<1> : k_grp_small<2>;
-    if (lds > 65536)
-      GDD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    fn<<<1, kGrpThr, lds, s>>>(n, labels, k, bits, perm, offsets, stop, step_i);
+  const GroupPlan p = group_plan(n, k);
+  GDD_REQUIRE(p.form != GROUP_INVALID, "group_by_label: k x tiles too large");
+  const int64_t cells = group_cells(n, k);
+  const GroupWs g = p.form == GROUP_SMALL ? GroupWs{} : carve_group(ws, p.form == GROUP_RADIX, cells);
+  if (g.bytes > ws_bytes) return fail(GDD_E_WORKSPACE, "group_by_label: workspace too small");
+  auto small = [&]() -> int {
+    auto fn = p.m == 1 ? k_grp_small<1> : k_grp_small<2>;
+    if (p.lds > 65536)
+      GDD_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    fn<<<1, kGrpThr, p.lds, s>>>(n, labels, k, p.bits, perm, offsets, stop, step_i);
     GDD_LAUNCHED();
     return GDD_OK;
-  }
-  if (k <= kCountMaxK) {
-    const GroupPlan p = group_plan(n, k);
-    const int64_t cells = (int64_t)k * p.ntiles;
-    GDD_REQUIRE(cells < INT_MAX, "group_by_label: k x tiles too large");
-    GroupWs g;
-    if (carve_group(ws, n, k, &g) > ws_bytes) return fail(GDD_E_WORKSPACE, "group_by_label: workspace too small");
-    int32_t *ghist = g.a, *gscan = g.b;
-    const size_t sb = g.sb;
-    void* sws = g.sws;
-    int bits = 1;
-    while ((1ll << bits) < (long long)k) ++bits;
-    const unsigned grid = (unsigned)((p.ntiles + p.waves - 1) / p.waves);
-    const size_t lds = sizeof(int32_t) * (size_t)p.waves * k;
-    auto go = [&](auto M_) -> int {
-      constexpr int M = decltype(M_)::value;
-      if (lds > 65536) {
-        GDD_HIP(hipFuncSetAttribute((const void*)k_grp_hist<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        GDD_HIP(hipFuncSetAttribute((const void*)k_grp_scatter<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      }
-      k_grp_hist<M><<<grid, 64 * p.waves, lds, s>>>(n, labels, k, p.ntiles, ghist, stop, step_i);
-      GDD_LAUNCHED();
-      int rc = exclusive_scan_i32(ghist, gscan, cells, sws, sb, s);
-      if (rc) return rc;
-      k_grp_scatter<M><<<grid, 64 * p.waves, lds, s>>>(n, labels, k, bits, p.ntiles, ghist, gscan, perm,
-                                                       offsets, stop, step_i);
-      GDD_LAUNCHED();
-      return GDD_OK;
-    };
-    switch (p.m) {
-      case 1: return go(std::integral_constant<int, 1>());
-      case 2: return go(std::integral_constant<int, 2>());
-      case 3: return go(std::integral_constant<int, 3>());
-      default: return go(std::integral_constant<int, 4>());
+  };
+  auto count = [&]() -> int {  // g.a: the histogram matrix, g.b: its scan
+    const int m = p.m;
+    auto hist = m == 1 ? k_grp_hist<1> : m == 2 ? k_grp_hist<2> : m == 3 ? k_grp_hist<3> : k_grp_hist<4>;
+    auto scat = m == 1 ? k_grp_scatter<1> : m == 2 ? k_grp_scatter<2> : m == 3 ? k_grp_scatter<3> : k_grp_scatter<4>;
+    if (p.lds > 65536) {
+      GDD_HIP(hipFuncSetAttribute((const void*)hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+      GDD_HIP(hipFuncSetAttribute((const void*)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
     }
-  }
-  // the radix path does not read the stop word: after a stop it regroups the (unchanged) labels
-  // into the workspace, which nothing reads any more
-  GroupWs g;
-  if (carve_group(ws, n, k, &g) > ws_bytes) return fail(GDD_E_WORKSPACE, "group_by_label: workspace too small");
-  int32_t *iota = g.a, *skeys = g.b;
-  const size_t sb = g.sb;
-  void* sws = g.sws;
-  int bits = 1;
-  while ((1ll << bits) < (long long)k) ++bits;
-  k_iota<<<blocks_of(n), 256, 0, s>>>(n, iota);
-  GDD_LAUNCHED();
-  int rc = sort_pairs_i32(labels, skeys, iota, perm, n, bits, sws, sb, s);
-  if (rc) return rc;
-  k_offsets<<<blocks_of(n + 1), 256, 0, s>>>(n, skeys, k, offsets);
-  GDD_LAUNCHED();
-  return GDD_OK;
+    hist<<<p.grid, 64 * p.waves, p.lds, s>>>(n, labels, k, p.ntiles, g.a, stop, step_i);
+    GDD_LAUNCHED();
+    if (int rc = exclusive_scan_i32(g.a, g.b, cells, g.sws, g.sb, s)) return rc;
+    scat<<<p.grid, 64 * p.waves, p.lds, s>>>(n, labels, k, p.bits, p.ntiles, g.a, g.b, perm, offsets, stop, step_i);
+    GDD_LAUNCHED();
+    return GDD_OK;
+  };
+  // g.a: the row ids, g.b: the sorted keys. Does not read the stop word: after a stop it regroups the
+  // (unchanged) labels into the workspace, which nothing reads any more. All 32 bits are sorted: the bits
+  // of keys clamped to k first would do, but need one more n-element buffer, a workspace change
+  auto radix = [&]() -> int {
+    k_iota<<<blocks_of(n), 256, 0, s>>>(n, g.a);
+    GDD_LAUNCHED();
+    if (int rc = sort_pairs_u32(labels, g.b, g.a, perm, n, g.sws, g.sb, s)) return rc;
+    k_offsets<<<blocks_of(n + 1), 256, 0, s>>>(n, g.b, k, offsets);
+    GDD_LAUNCHED();
+    return GDD_OK;
+  };
+  return p.form == GROUP_SMALL ? small() : p.form == GROUP_COUNT ? count() : radix();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -358,27 +356,49 @@ constexpr int kFoldSmallAvgRows = 64;
 constexpr int kFoldMaxR = 1024;
 constexpr int64_t kFoldPadMinRows = 65536;  // the M-step folds a zero-padded copy of X from here (dim % 4 != 0)
 
+// The fold kernels' argument, built by fold_sums / fold_means and the setters; fold_launch fills in fw_max .. Rmax.
 struct FoldArgs {
-  int dim, fw_max, R;
+  int dim = 0, fw_max = 0, R = 0;
   // clusters of at least big_rows members (0: none) are folded in feature slices of fw_big columns,
   // one workgroup per slice, R_big rows per chunk; Rmax = max(R, R_big) sizes the LDS id ring
-  int big_rows, fw_big, R_big, Rmax;
-  int c0;                  // first cluster of this launch; outputs are indexed from c0 (a slice)
-  const float* X;
-  const float* w;          // Lloyd sample weights (nullable: unit weights)
-  const int32_t* perm;
-  const int32_t* offsets;
-  float* out;              // k x dim: sums (Lloyd) or means
-  float* wsum;             // Lloyd weight sums
-  long long* counts;       // mean: members per cluster (nullable)
-  int empty_as_zero;
-  const int32_t* stop;
-  int step_i;
+  int big_rows = 0, fw_big = 0, R_big = 0, Rmax = 0;
+  int c0 = 0;                        // first cluster of this launch; outputs are indexed from c0 (a slice)
+  const float* X = nullptr;
+  const float* w = nullptr;          // Lloyd sample weights (nullable: unit weights)
+  const int32_t* perm = nullptr;
+  const int32_t* offsets = nullptr;
+  float* out = nullptr;              // k x dim: sums (Lloyd) or means
+  float* wsum = nullptr;             // Lloyd weight sums
+  long long* counts = nullptr;       // mean: members per cluster (nullable)
+  int empty_as_zero = 0;
+  const int32_t* stop = nullptr;
+  int step_i = 0;
   int ld = 0;  // row stride of X (0: dim). A column range [f0, f1) folds X + f0 with dim = f1 - f0
   int64_t avg_rows = 0;  // members per cluster on average (0: unknown); small averages fold in 8 KiB chunks
   int out_dim = 0;  // output row stride and columns written (0: dim); folding a zero-padded copy of X
                     // (dim a multiple of 4) writes only its first out_dim columns
+
+  FoldArgs& columns(int f0, int f1, int ld_) { X += f0; dim = f1 - f0; ld = ld_; return *this; }
+  FoldArgs& padded(const float* Xp, int dp) { X = Xp; out_dim = dim; dim = dp; return *this; }
+  FoldArgs& gate(const int32_t* stop_, int step) { stop = stop_; step_i = step; return *this; }
 };
+
+// Lloyd sums of k clusters over n rows (w nullable: unit weights)
+FoldArgs fold_sums(int64_t n, int k, int dim, const float* X, const float* w, const int32_t* perm,
+                   const int32_t* offsets, float* sums, float* wsum) {
+  FoldArgs a;
+  a.dim = dim; a.X = X; a.w = w; a.perm = perm; a.offsets = offsets; a.out = sums; a.wsum = wsum;
+  a.avg_rows = n / k;
+  return a;
+}
+// cluster means (fp64 chains)
+FoldArgs fold_means(int dim, const float* X, const int32_t* perm, const int32_t* offsets, float* means,
+                    long long* counts, int empty_as_zero) {
+  FoldArgs a;
+  a.dim = dim; a.X = X; a.perm = perm; a.offsets = offsets; a.out = means; a.counts = counts;
+  a.empty_as_zero = empty_as_zero;
+  return a;
+}
 
 template <typename ACC, bool WEIGHTED>
 __device__ __forceinline__ void fold_col(const float* __restrict__ col, int stride, int rp, ACC& acc,
@@ -743,82 +763,77 @@ __global__ __launch_bounds__(256) void k_seg_fold_cm(const FoldArgs a) {
   if (blockIdx.x == 0 && tid == 255) a.wsum[cs] = fminf((float)nm, 16777216.f);
 }
 
-// clusters [a0.c0, a0.c0 + count): launches of at most kFoldMaxGridY clusters (grid.y), each
-// writing its slice of the outputs
+// Which kernel a fold launches and its chunk geometry; host only.
+struct FoldPlan {
+  bool cm;  // the column-major kernel: unit-weight Lloyd sums over 16-byte aligned rows, FW <= 64
+  bool mean, small, weighted, vec;  // otherwise the k_seg_fold instantiation
+  int fw_max, R, big_rows, fw_big, R_big, Rmax;  // FoldArgs' geometry
+  unsigned slices;                               // grid.x
+  int elems;                                     // floats per LDS chunk buffer
+  size_t lds;
+};
+
+// ld: the row stride (0: dim); x_aligned: X is 16-byte aligned; big_rows: the caller's (0: no slicing)
+FoldPlan fold_plan(int dim, int ld, bool weighted, bool mean, int64_t avg_rows, int big_rows, bool x_aligned) {
+  FoldPlan p{};
+  p.mean = mean;
+  p.weighted = weighted;
+  p.fw_max = std::min(dim, weighted ? 192 : 256);  // weighted: thread 255 folds the weights
+  p.small = !mean && avg_rows > 0 && avg_rows <= kFoldSmallAvgRows && dim <= 128;
+  p.elems = mean ? kFoldElemsMean : (p.small ? kFoldElemsSmall : kFoldElemsMax);
+  p.R = std::max(16, std::min(kFoldMaxR, p.elems / p.fw_max) & ~15);
+  p.vec = dim % 4 == 0 && (ld ? ld : dim) % 4 == 0 && p.fw_max % 4 == 0 && x_aligned;
+  p.slices = (unsigned)((dim + p.fw_max - 1) / p.fw_max);
+  p.fw_big = p.fw_max;  // not sliced
+  p.R_big = p.R;
+  constexpr int kSliceCols = 16;  // columns per slice of a large cluster (a multiple of 4)
+  if (big_rows > 0 && !mean && p.fw_max > kSliceCols) {
+    p.big_rows = big_rows;
+    p.fw_big = kSliceCols;
+    p.R_big = std::max(16, std::min(kFoldMaxR, p.elems / kSliceCols) & ~15);
+    p.slices = std::max<unsigned>(p.slices, (unsigned)((dim + kSliceCols - 1) / kSliceCols));
+  }
+  p.Rmax = std::max(p.R, p.R_big);
+  p.cm = !mean && !weighted && !p.small && p.vec && p.fw_max <= 64 && p.fw_big <= 64;
+  // cm: two column-major chunk buffers of FW x (R + 4) floats
+  p.lds = sizeof(float) * (p.cm ? 2 * std::max<size_t>((size_t)p.fw_max * (p.R + 4), (size_t)p.fw_big * (p.R_big + 4))
+                                : 2 * (size_t)p.elems + 3 * (size_t)p.Rmax * (weighted ? 2 : 1));
+  return p;
+}
+
+// clusters [c0, c0 + count), written as a slice from c0 on: plan, then launches of at most kFoldMaxGridY (grid.y)
 constexpr int kFoldMaxGridY = 65535;
-int fold_launch_one(const FoldArgs& a0, int count, bool mean, hipStream_t s);
-int fold_launch(const FoldArgs& a0, int count, bool mean, hipStream_t s) {
+int fold_launch(const FoldArgs& a0, int c0, int count, bool mean, hipStream_t s) {
   GDD_REQUIRE(count >= 0, "cluster fold: %d clusters", count);
+  const FoldPlan p = fold_plan(a0.dim, a0.ld, !mean && a0.w, mean, a0.avg_rows, a0.big_rows,
+                               (reinterpret_cast<uintptr_t>(a0.X) & 15) == 0);
+  FoldArgs a = a0;
+  a.fw_max = p.fw_max; a.R = p.R; a.big_rows = p.big_rows; a.fw_big = p.fw_big; a.R_big = p.R_big; a.Rmax = p.Rmax;
+  using Kern = void (*)(const FoldArgs);
+  static const Kern seg[] = {  // <ACC, VEC, WEIGHTED, MEAN, elems> at mean << 3 | small << 2 | weighted << 1 | vec
+      k_seg_fold<float, false, false, false>, k_seg_fold<float, true, false, false>,
+      k_seg_fold<float, false, true, false>, k_seg_fold<float, true, true, false>,
+      k_seg_fold<float, false, false, false, kFoldElemsSmall>, k_seg_fold<float, true, false, false, kFoldElemsSmall>,
+      k_seg_fold<float, false, true, false, kFoldElemsSmall>, k_seg_fold<float, true, true, false, kFoldElemsSmall>,
+      k_seg_fold<double, false, false, true, kFoldElemsMean>, k_seg_fold<double, true, false, true, kFoldElemsMean>};
+  const Kern kern = p.cm ? k_seg_fold_cm : seg[p.mean << 3 | p.small << 2 | p.weighted << 1 | p.vec];
   for (int off = 0; off < count; off += kFoldMaxGridY) {
-    FoldArgs a = a0;
-    a.c0 = a0.c0 + off;
+    a.c0 = c0 + off;
     a.out = a0.out + (int64_t)off * (a0.out_dim ? a0.out_dim : a0.dim);
     if (a0.wsum) a.wsum = a0.wsum + off;
     if (a0.counts) a.counts = a0.counts + off;
-    const int rc = fold_launch_one(a, std::min(kFoldMaxGridY, count - off), mean, s);
-    if (rc) return rc;
+    GDD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    kern<<<dim3(p.slices, (unsigned)std::min(kFoldMaxGridY, count - off)), 256, p.lds, s>>>(a);
+    GDD_LAUNCHED();
   }
   return GDD_OK;
 }
 
-int fold_launch_one(const FoldArgs& a0, int count, bool mean, hipStream_t s) {
-  FoldArgs a = a0;
-  const bool weighted = a.w != nullptr;
-  a.fw_max = std::min(a.dim, weighted ? 192 : 256);  // weighted: thread 255 folds the weights
-  if (a.fw_max % 4 != 0 && a.fw_max < a.dim) a.fw_max &= ~3;
-  const bool small = !mean && a.avg_rows > 0 && a.avg_rows <= kFoldSmallAvgRows && a.dim <= 128;
-  const int elems = mean ? kFoldElemsMean : (small ? kFoldElemsSmall : kFoldElemsMax);
-  int R = std::min(kFoldMaxR, elems / a.fw_max);
-  R &= ~15;
-  a.R = std::max(R, 16);
-  const int ldx = a.ld ? a.ld : a.dim;
-  const bool vec = a.dim % 4 == 0 && ldx % 4 == 0 && a.fw_max % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;
-  unsigned nsl = (unsigned)((a.dim + a.fw_max - 1) / a.fw_max);
-  constexpr int kSliceCols = 16;  // columns per slice of a large cluster (a multiple of 4)
-  if (a.big_rows > 0 && !mean && a.fw_max > kSliceCols) {
-    a.fw_big = kSliceCols;
-    a.R_big = std::max(16, std::min(kFoldMaxR, elems / kSliceCols) & ~15);
-    nsl = std::max<unsigned>(nsl, (unsigned)((a.dim + kSliceCols - 1) / kSliceCols));
-  } else {
-    a.big_rows = 0;
-    a.fw_big = a.fw_max;
-    a.R_big = a.R;
-  }
-  a.Rmax = std::max(a.R, a.R_big);
-  if (count == 0) return GDD_OK;
-  dim3 grid(nsl, (unsigned)count);
-  {  // unit-weight Lloyd sums over 16-byte aligned rows: the column-major form
-    if (!mean && !weighted && !small && vec && a.fw_max <= 64 && a.fw_big <= 64) {
-      const size_t bufsz = std::max<size_t>((size_t)a.fw_max * (a.R + 4), (size_t)a.fw_big * (a.R_big + 4));
-      const size_t lds_cm = sizeof(float) * 2 * bufsz;
-      GDD_HIP(hipFuncSetAttribute((const void*)k_seg_fold_cm, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_cm));
-      k_seg_fold_cm<<<grid, 256, lds_cm, s>>>(a);
-      GDD_LAUNCHED();
-      return GDD_OK;
-    }
-  }
-  const size_t lds = sizeof(float) * (2 * (size_t)elems + 3 * (size_t)a.Rmax * (weighted ? 2 : 1));
-  auto go = [&](auto kern) -> int {
-    GDD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kern<<<grid, 256, lds, s>>>(a);
-    GDD_LAUNCHED();
-    return GDD_OK;
-  };
-  if (mean)
-    return vec ? go(k_seg_fold<double, true, false, true, kFoldElemsMean>)
-               : go(k_seg_fold<double, false, false, true, kFoldElemsMean>);
-  if (small) {
-    if (weighted)
-      return vec ? go(k_seg_fold<float, true, true, false, kFoldElemsSmall>)
-                 : go(k_seg_fold<float, false, true, false, kFoldElemsSmall>);
-    return vec ? go(k_seg_fold<float, true, false, false, kFoldElemsSmall>)
-               : go(k_seg_fold<float, false, false, false, kFoldElemsSmall>);
-  }
-  if (weighted)
-    return vec ? go(k_seg_fold<float, true, true, false>) : go(k_seg_fold<float, false, true, false>);
-  return vec ? go(k_seg_fold<float, true, false, false>) : go(k_seg_fold<float, false, false, false>);
+// M-step: clusters above fold_slice x the mean size (default 1.5; 0: off) and of at least 4096 members
+// fold in slices; both drivers' FoldArgs::big_rows
+int fold_big_rows(int64_t n, int k) {
+  const double f = forced_value("fold_slice", 1.5);
+  return f > 0.0 ? (int)std::min<double>(std::max(f * (double)n / (double)k, 4096.0), (double)INT_MAX) : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1298,13 +1313,21 @@ extern "C" int gdd_group_by_label(int64_t n, const int32_t* labels, int k, int32
   return group_dev(n, labels, k, perm, offsets, ws, ws_bytes, nullptr, 0, to_hip(stream));
 }
 
+extern "C" const char* gdd_group_path(int64_t n, int k) {  // small/m1|m2, count/m<M>/w<W>, radix
+  static thread_local char name[32];
+  const GroupPlan p = n > 0 && k > 0 ? group_plan(n, k) : GroupPlan{};
+  if (p.form == GROUP_INVALID) return "invalid";
+  if (p.form == GROUP_RADIX) return "radix";
+  snprintf(name, sizeof name, p.form == GROUP_SMALL ? "small/m%d" : "count/m%d/w%d", p.m, p.waves);
+  return name;
+}
+
 extern "C" int gdd_segment_sum_f32(int64_t n, int dim, const float* X, const float* w,
                                    const int32_t* perm, const int32_t* offsets, int k, float* sums,
                                    float* wsum, gdd_stream_t stream) {
   GDD_REQUIRE(n > 0 && dim > 0 && k > 0 && X && perm && offsets && sums && wsum,
               "segment_sum_f32: bad arguments");
-  FoldArgs a{dim, 0, 0, 0, 0, 0, 0, 0, X, w, perm, offsets, sums, wsum, nullptr, 0, nullptr, 0, 0, n / k};
-  return fold_launch(a, k, false, to_hip(stream));
+  return fold_launch(fold_sums(n, k, dim, X, w, perm, offsets, sums, wsum), 0, k, false, to_hip(stream));
 }
 
 extern "C" int gdd_segment_sum_f32_part(int64_t n, int dim, const float* X, const float* w,
@@ -1314,8 +1337,8 @@ extern "C" int gdd_segment_sum_f32_part(int64_t n, int dim, const float* X, cons
   GDD_REQUIRE(n > 0 && dim > 0 && k > 0 && 0 <= c0 && c0 <= c1 && c1 <= k && X && perm && offsets &&
                   (c0 == c1 || (sums_part && wsum_part)),
               "segment_sum_f32_part: bad arguments");
-  FoldArgs a{dim, 0, 0, 0, 0, 0, 0, c0, X, w, perm, offsets, sums_part, wsum_part, nullptr, 0, nullptr, 0, 0, n / k};
-  return fold_launch(a, c1 - c0, false, to_hip(stream));
+  return fold_launch(fold_sums(n, k, dim, X, w, perm, offsets, sums_part, wsum_part), c0, c1 - c0, false,
+                     to_hip(stream));
 }
 
 extern "C" int gdd_cluster_mean(int64_t n, int d, const float* feat, const int32_t* perm,
@@ -1323,8 +1346,7 @@ extern "C" int gdd_cluster_mean(int64_t n, int d, const float* feat, const int32
                                 long long* counts, gdd_stream_t stream) {
   GDD_REQUIRE(n > 0 && d > 0 && k > 0 && feat && perm && offsets && feat_syn,
               "cluster_mean: bad arguments");
-  FoldArgs a{d, 0, 0, 0, 0, 0, 0, 0, feat, nullptr, perm, offsets, feat_syn, nullptr, counts, empty_as_zero, nullptr, 0};
-  return fold_launch(a, k, true, to_hip(stream));
+  return fold_launch(fold_means(d, feat, perm, offsets, feat_syn, counts, empty_as_zero), 0, k, true, to_hip(stream));
 }
 
 extern "C" int gdd_cluster_mean_part(int64_t n, int d, const float* feat, const int32_t* perm,
@@ -1333,9 +1355,8 @@ extern "C" int gdd_cluster_mean_part(int64_t n, int d, const float* feat, const 
   GDD_REQUIRE(n > 0 && d > 0 && k > 0 && 0 <= c0 && c0 <= c1 && c1 <= k && feat && perm && offsets &&
                   (c0 == c1 || feat_part),
               "cluster_mean_part: bad arguments");
-  FoldArgs a{d, 0, 0, 0, 0, 0, 0, c0, feat, nullptr, perm, offsets, feat_part, nullptr, counts_part, empty_as_zero,
-             nullptr, 0};
-  return fold_launch(a, c1 - c0, true, to_hip(stream));
+  return fold_launch(fold_means(d, feat, perm, offsets, feat_part, counts_part, empty_as_zero), c0, c1 - c0, true,
+                     to_hip(stream));
 }
 
 extern "C" int gdd_average_centers(int k, int dim, float* C_new, const float* wsum,
@@ -1362,8 +1383,21 @@ extern "C" size_t gdd_lloyd_state_bytes(void) { return sizeof(LloydState); }
 // slower, §4); a copy with rows of round4(dim) floats, made once per run, lets it gather 16-byte
 // pieces of aligned rows. Each column's chain is unchanged and the pad columns are not written, so the
 // sums are the same bits.
-static int fold_pad_dim(int64_t n, int dim) {
-  return (dim % 4 != 0 && n >= kFoldPadMinRows) ? (dim + 3) & ~3 : 0;
+static int fold_pad_dim(int64_t n, int dim) { return dim % 4 != 0 && n >= kFoldPadMinRows ? (dim + 3) & ~3 : 0; }
+
+extern "C" const char* gdd_fold_path(int64_t n, int dim, int ld, int k, int flags, int big_rows) {
+  const bool mean = flags & GDD_FOLD_MEAN, weighted = flags & GDD_FOLD_WEIGHTED;
+  if (n <= 0 || dim <= 0 || ld < 0 || k <= 0 || (mean && weighted)) return "invalid";
+  const int big = big_rows < 0 ? fold_big_rows(n, k) : big_rows;  // < 0: the M-step's own rule
+  const FoldPlan p = fold_plan(dim, ld, weighted, mean, mean ? 0 : n / k, big, !(flags & GDD_FOLD_X_UNALIGNED));
+  // cm/<fw>x<R>[/sliced<R_big>], seg/f32|mean/vec|scalar[/w][/small]/<slices>x<R>[/sliced<R_big>]
+  static thread_local char name[64];
+  int len = snprintf(name, sizeof name, "cm/%dx%d", p.fw_max, p.R);
+  if (!p.cm)
+    len = snprintf(name, sizeof name, "seg/%s/%s%s%s/%ux%d", p.mean ? "mean" : "f32", p.vec ? "vec" : "scalar",
+                   p.weighted ? "/w" : "", p.small ? "/small" : "", p.slices, p.R);
+  if (p.big_rows) snprintf(name + len, sizeof name - len, "/sliced%d", p.R_big);
+  return name;
 }
 
 __global__ void k_pad_rows(int64_t n, int dim, int dp, const float* __restrict__ X, float* __restrict__ Xp) {
@@ -1441,6 +1475,125 @@ extern "C" size_t gdd_kmeans_lloyd_ws_bytes(int64_t n, int dim, int k) {
 
 extern "C" size_t gdd_kmeans_lloyd_host_ws_bytes(void) { return 4 * sizeof(LloydState); }
 
+// C_new[c][f] = the ranks' column slices of the sums side by side: rank r's slot (k * fw floats at
+// r * k * fw) holds its k x w_r block row-major, w_r = min(fw, dim - r * fw) columns
+static __global__ void k_assemble_cols(int k, int dim, int fw, const float* __restrict__ parts,
+                                       float* __restrict__ C_new, const int32_t* stop, int step_i) {
+  if (stopped(stop, step_i)) return;
+  const int64_t total = (int64_t)k * dim;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(e / dim), f = (int)(e - (int64_t)c * dim);
+    const int r = f / fw, w = min(fw, dim - r * fw);
+    C_new[e] = parts[(int64_t)r * k * fw + (int64_t)c * w + (f - r * fw)];
+  }
+}
+
+// unit weights: the weight sums the fold writes (a sequential fp32 count, which sticks at 2^24), for
+// a rank that folds no columns
+static __global__ void k_wsum_offsets(int k, const int32_t* __restrict__ offsets, float* __restrict__ wsum,
+                                      const int32_t* stop, int step_i) {
+  if (stopped(stop, step_i)) return;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < k) wsum[c] = fminf((float)(offsets[c + 1] - offsets[c]), 16777216.f);
+}
+
+// ---- one Lloyd iteration: the step launchers of both drivers ----------------------------------------
+// Iteration `it` is steps 2 it (E-step, M-step) and 2 it + 1 (update); what the drivers do differently is an argument.
+struct LloydStep {
+  int64_t n;
+  int dim, k;
+  const LloydWs* lw;
+  LloydState* st;
+  int it;
+  const float* C;  // the centres the E-step reads and the update's shifts are measured from
+};
+
+// bounded E-steps where the top-2 pass fits (GDD_FORCE=lloyd_no_prune: every row every iteration)
+static bool lloyd_bounded(int dim, int k) { return !forced("lloyd_no_prune") && lloyd_prune_ok(dim, k); }
+
+// first: the first E-step of a fit or after a relocation sets the rows' bounds and does not read shift.
+// Xpad, dpad: the zero-padded copy for the top-2 pass's row lists (null: X), which only the run makes.
+// bounded: lloyd_bounded(dim, k), the caller's so that the run reads it once, not per iteration.
+// norms_at_first: the phase driver's first E-step takes its rows' norms; the run takes them before its loop.
+// listlen: the GDD_LLOYD_LISTLEN diagnostic (it synchronises) is the run's alone.
+static int lloyd_estep_launch(const LloydStep& a, const float* X, int64_t r0, int64_t r1, int32_t* labels,
+                              const float* shift, bool first, const float* Xpad, int dpad, bool bounded,
+                              bool norms_at_first, bool listlen, hipStream_t s) {
+  const LloydWs& w = *a.lw;
+  const int32_t* stop = &a.st->stop_at;
+  const int sa = 2 * a.it, dim = a.dim, k = a.k;
+  const int64_t m = r1 - r0;
+  const float* Xr = X + r0 * dim;
+  labels += r0;
+  if (!bounded) return kmeans_assign_dev(m, dim, Xr, k, a.C, w.cn2, labels, w.keys, stop, sa, s);
+  const double kappa = (2.0 * dim + 8.0) * kEps32;
+  if (first && norms_at_first) {
+    k_row_norm64<<<blocks_of(m, 64), 256, 0, s>>>(m, dim, Xr, w.xn + r0);
+    GDD_LAUNCHED();
+  }
+  k_ham_centres<<<k + 1, 256, 0, s>>>(k, dim, a.C, shift, first ? 0 : 1, w.sep, w.glob, w.count, stop, sa);
+  GDD_LAUNCHED();
+  if (!first) {
+    k_ham_test<<<blocks_of(m, 256 * kHamRows), 256, 0, s>>>(m, dim, labels, w.xn + r0, w.ub + r0, w.lb + r0, shift,
+                                                             w.sep, w.glob, kappa, w.list, w.count, stop, sa);
+    GDD_LAUNCHED();
+    if (listlen && getenv("GDD_LLOYD_LISTLEN")) {  // diagnostics: the bounded E-step's row count
+      int64_t cnt = 0;
+      GDD_HIP(hipMemcpyAsync(&cnt, w.count, sizeof(cnt), hipMemcpyDeviceToHost, s));
+      GDD_HIP(hipStreamSynchronize(s));
+      fprintf(stderr, "lloyd iteration %d: %lld of %lld rows listed\n", a.it, (long long)cnt, (long long)m);
+    }
+  }
+  if (int rc = kmeans_assign_top2_dev(m, dim, Xr, first ? nullptr : w.list, first ? nullptr : w.count, k, a.C, w.cn2,
+                                      w.keys, w.sec, stop, sa, s, Xpad, dpad))
+    return rc;
+  k_ham_finalize<<<std::min<unsigned>(blocks_of(m), 2048), 256, 0, s>>>(
+      w.count, m, first ? nullptr : w.list, w.keys, w.sec, w.xn + r0, w.glob, kappa, labels, w.ub + r0, w.lb + r0,
+      stop, sa);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+// fold: the sums' FoldArgs, gated here; a rank that folds no columns (dim 0) writes fold.wsum from the offsets.
+// check_empty: the phase driver launches the empty-cluster check; the run's update carries it (check_st).
+static int lloyd_mstep_launch(const LloydStep& a, const int32_t* labels, const FoldArgs& fold, bool check_empty,
+                              hipStream_t s) {
+  const LloydWs& w = *a.lw;
+  const int32_t* stop = &a.st->stop_at;
+  const int sa = 2 * a.it;
+  if (int rc = group_dev(a.n, labels, a.k, w.perm, w.offsets, w.gws, w.gb, stop, sa, s)) return rc;
+  if (fold.dim > 0) {
+    if (int rc = fold_launch(FoldArgs(fold).gate(stop, sa), 0, a.k, false, s)) return rc;
+  } else {
+    k_wsum_offsets<<<blocks_of(a.k), 256, 0, s>>>(a.k, w.offsets, fold.wsum, stop, sa);
+    GDD_LAUNCHED();
+  }
+  if (check_empty) {
+    k_lloyd_check_empty<<<1, 256, 0, s>>>(a.k, fold.wsum, a.st, a.it, sa);
+    GDD_LAUNCHED();
+  }
+  return GDD_OK;
+}
+
+// C_new holds the sums and becomes the centres. check_st: the run's average carries the M-step's empty-
+// cluster check (not on a resumed iteration, whose M-step ran before the relocation).
+// labels_old null: the fixed-point driver counts the changed labels in its all-reduce, not here.
+static int lloyd_update_launch(const LloydStep& a, float* C_new, const float* wsum, float* shift, double tol,
+                               const int32_t* labels, int32_t* labels_old, bool check_st, hipStream_t s) {
+  const int sb = 2 * a.it + 1;
+  k_avg_centers<<<a.k, 64, 0, s>>>(a.k, a.dim, C_new, wsum, a.C, shift, &a.st->stop_at, sb,
+                                   check_st ? a.st : nullptr, check_st ? a.it : 0);
+  GDD_LAUNCHED();
+  if (labels_old) {
+    k_lloyd_changed<<<std::min<unsigned>(blocks_of(a.n), 2048), 256, 0, s>>>(a.n, labels, labels_old, a.st, sb);
+    GDD_LAUNCHED();
+  }
+  k_lloyd_converge<<<1, 256, 0, s>>>(a.k, shift, tol, a.st, a.it, sb);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
 extern "C" int gdd_kmeans_lloyd_run(int64_t n, int dim, const float* X, int k, float* C0, float* C1,
                                     int32_t* labels, int32_t* labels_old, float* wsum, float* shift,
                                     int it0, int resume, int max_iter, double tol, void* state,
@@ -1457,108 +1610,43 @@ extern "C" int gdd_kmeans_lloyd_run(int64_t n, int dim, const float* X, int k, f
   hipStream_t s = to_hip(stream);
   LloydWs lw;
   if (!carve_lloyd(ws, ws_bytes, n, dim, k, &lw)) return fail(GDD_E_WORKSPACE, "kmeans_lloyd_run: workspace too small");
-  auto* keys = lw.keys;
-  float* cn2 = lw.cn2;
-  int32_t* perm = lw.perm;
-  int32_t* offsets = lw.offsets;
-  const size_t gb = lw.gb;
-  void* gws = lw.gws;
-  double* xn = lw.xn;
-  double* ub = lw.ub;
-  double* lb = lw.lb;
-  int64_t* list = lw.list;
-  float* sec = lw.sec;
-  double* sep = lw.sep;
-  double* glob = lw.glob;
-  int64_t* count = lw.count;
-  // bounded E-steps (GDD_FORCE=lloyd_no_prune: every row every iteration), from the run's first E-step on
-  const bool prune = !forced("lloyd_no_prune") && lloyd_prune_ok(dim, k);
-  const int prune_first = resume ? it0 + 1 : it0;
-  const double kappa = (2.0 * dim + 8.0) * kEps32;
-  const unsigned fgrid = std::min<unsigned>(blocks_of(n), 2048);
-  if (prune) {
-    k_row_norm64<<<blocks_of(n, 64), 256, 0, s>>>(n, dim, X, xn);
-    GDD_LAUNCHED();
-  }
   LloydState* st = static_cast<LloydState*>(state);
   LloydState* hs = static_cast<LloydState*>(host_ws);
+  LloydStep a{n, dim, k, &lw, st};
+  const float* Xpad = nullptr;  // the padded copy where the E-step reads it
+  const bool bounded = lloyd_bounded(dim, k);       // from the run's first E-step on
+  const int bounds_first = resume ? it0 + 1 : it0;  // ... which sets the rows' bounds
+  if (bounded) {
+    k_row_norm64<<<blocks_of(n, 64), 256, 0, s>>>(n, dim, X, lw.xn);
+    GDD_LAUNCHED();
+  }
   // a fresh run (or a resume after the host's relocation) starts with the stop word clear; the
   // changed flag is kept on resume (the E-step that set it already ran)
   GDD_HIP(hipMemsetAsync(st, 0, offsetof(LloydState, changed), s));
   if (!resume) GDD_HIP(hipMemsetAsync(&st->changed, 0, sizeof(int32_t), s));
-  FoldArgs fa{dim, 0, 0, 0, 0, 0, 0, 0, X, nullptr, perm, offsets, nullptr, wsum, nullptr, 0, &st->stop_at, 0};
-  fa.avg_rows = n / k;
-  const float* Xpad = nullptr;  // the padded copy for the bounded E-step's row lists (estep_no_pad: X)
-  int dpad = 0;
-  {  // the fold's zero-padded copy of X at the end of the workspace (fold_no_pad: gather X itself)
-    const int dp = fold_pad_dim(n, dim);
-    if (lw.Xp && !forced("fold_no_pad")) {
-      float* Xp = lw.Xp;
-      const int64_t total = n * (dp / 4);
-      k_pad_rows<<<(unsigned)std::min<int64_t>((total + 255) / 256, 8192), 256, 0, s>>>(n, dim, dp, X, Xp);
-      GDD_LAUNCHED();
-      fa.X = Xp;
-      fa.dim = dp;
-      fa.out_dim = dim;
-      if (!forced("estep_no_pad")) {
-        Xpad = Xp;
-        dpad = dp;
-      }
-    }
+  FoldArgs fa = fold_sums(n, k, dim, X, nullptr, lw.perm, lw.offsets, nullptr, wsum);
+  fa.big_rows = fold_big_rows(n, k);
+  // the fold's zero-padded copy of X at the end of the workspace (fold_no_pad: none), which the bounded
+  // E-step's row lists read too (estep_no_pad: X); only this driver makes one
+  const int dp = fold_pad_dim(n, dim);
+  if (dp && !forced("fold_no_pad")) {
+    const int64_t total = n * (dp / 4);
+    k_pad_rows<<<(unsigned)std::min<int64_t>((total + 255) / 256, 8192), 256, 0, s>>>(n, dim, dp, X, lw.Xp);
+    GDD_LAUNCHED();
+    fa.padded(lw.Xp, dp);
+    if (!forced("estep_no_pad")) Xpad = lw.Xp;
   }
-  {  // M-step: clusters above fold_slice x the mean size (default 1.5; 0: off) fold in slices
-    const double f = forced_value("fold_slice", 1.5);
-    const double rows = f * (double)n / (double)k;
-    fa.big_rows = f > 0.0 ? (int)std::min<double>(std::max(rows, 4096.0), (double)INT_MAX) : 0;
-  }
-  const unsigned cgrid = std::min<unsigned>(blocks_of(n), 2048);
-  auto enqueue = [&](int i, bool phase_a) -> int {
-    float* cin = (i & 1) ? C1 : C0;
-    float* cout = (i & 1) ? C0 : C1;
-    const int sa = 2 * i, sb = 2 * i + 1;
+  auto enqueue = [&](int i, bool phase_a) -> int {  // phase_a: not the resumed iteration, whose labels and sums stand
+    a.it = i;
+    a.C = (i & 1) ? C1 : C0;
+    fa.out = (i & 1) ? C0 : C1;
     if (phase_a) {
-      int rc;
-      if (prune) {
-        const bool first = i == prune_first;
-        k_ham_centres<<<k + 1, 256, 0, s>>>(k, dim, cin, shift, first ? 0 : 1, sep, glob, count,
-                                            &st->stop_at, sa);
-        GDD_LAUNCHED();
-        if (!first) {
-          k_ham_test<<<blocks_of(n, 256 * kHamRows), 256, 0, s>>>(n, dim, labels, xn, ub, lb, shift, sep, glob, kappa,
-                                                 list, count, &st->stop_at, sa);
-          GDD_LAUNCHED();
-          if (getenv("GDD_LLOYD_LISTLEN")) {  // diagnostics: the bounded E-step's row count (synchronises)
-            int64_t cnt = 0;
-            GDD_HIP(hipMemcpyAsync(&cnt, count, sizeof(cnt), hipMemcpyDeviceToHost, s));
-            GDD_HIP(hipStreamSynchronize(s));
-            fprintf(stderr, "lloyd iteration %d: %lld of %lld rows listed\n", i, (long long)cnt, (long long)n);
-          }
-        }
-        rc = kmeans_assign_top2_dev(n, dim, X, first ? nullptr : list, first ? nullptr : count, k, cin,
-                                    cn2, keys, sec, &st->stop_at, sa, s, Xpad, dpad);
-        if (rc) return rc;
-        k_ham_finalize<<<fgrid, 256, 0, s>>>(count, n, first ? nullptr : list, keys, sec, xn, glob,
-                                             kappa, labels, ub, lb, &st->stop_at, sa);
-        GDD_LAUNCHED();
-      } else {
-        rc = kmeans_assign_dev(n, dim, X, k, cin, cn2, labels, keys, &st->stop_at, sa, s);
-        if (rc) return rc;
-      }
-      rc = group_dev(n, labels, k, perm, offsets, gws, gb, &st->stop_at, sa, s);
-      if (rc) return rc;
-      fa.out = cout;
-      fa.step_i = sa;
-      rc = fold_launch(fa, k, false, s);
-      if (rc) return rc;
-      // the empty-cluster check rides in the average's launch (check_st)
+      if (int rc = lloyd_estep_launch(a, X, 0, n, labels, shift, /*first=*/i == bounds_first, Xpad, Xpad ? dp : 0,
+                                      bounded, /*norms_at_first=*/false, /*listlen=*/true, s))
+        return rc;
+      if (int rc = lloyd_mstep_launch(a, labels, fa, /*check_empty=*/false, s)) return rc;
     }
-    k_avg_centers<<<k, 64, 0, s>>>(k, dim, cout, wsum, cin, shift, &st->stop_at, sb, phase_a ? st : nullptr, i);
-    GDD_LAUNCHED();
-    k_lloyd_changed<<<cgrid, 256, 0, s>>>(n, labels, labels_old, st, sb);
-    GDD_LAUNCHED();
-    k_lloyd_converge<<<1, 256, 0, s>>>(k, shift, tol, st, i, sb);
-    GDD_LAUNCHED();
-    return GDD_OK;
+    return lloyd_update_launch(a, fa.out, wsum, shift, tol, labels, labels_old, /*check_st=*/phase_a, s);
   };
   // chunks of iterations enqueued ahead of the decision; the host reads the state of chunk c while
   // chunk c+1 runs (two pinned slots, one event each)
@@ -1617,75 +1705,19 @@ extern "C" int gdd_kmeans_lloyd_run(int64_t n, int dim, const float* X, int k, f
 // ---- one Lloyd iteration in three phases, for a process group (gdd.sharded.ShardedKMeans) --------
 // Rank r runs the bounded E-step on its rows and the M-step fold on its columns; the caller
 // all-gathers the labels and the column slices of the sums in between (RCCL, stream-ordered), and
-// every rank runs the same replicated update. Every kernel is gated by the stop word exactly as in
-// gdd_kmeans_lloyd_run (iteration i = steps 2i and 2i+1), so the host enqueues chunks of iterations
-// and reads the state once per chunk. Each value comes from the single-GPU kernels on the same
-// operands: labels, sums, centres, iteration counts are bit-identical for every world size.
-namespace gdd {
-namespace {
-// C_new[c][f] = the ranks' column slices of the sums side by side: rank r's slot (k * fw floats at
-// r * k * fw) holds its k x w_r block row-major, w_r = min(fw, dim - r * fw) columns
-__global__ void k_assemble_cols(int k, int dim, int fw, const float* __restrict__ parts,
-                                float* __restrict__ C_new, const int32_t* stop, int step_i) {
-  if (stopped(stop, step_i)) return;
-  const int64_t total = (int64_t)k * dim;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(e / dim), f = (int)(e - (int64_t)c * dim);
-    const int r = f / fw, w = min(fw, dim - r * fw);
-    C_new[e] = parts[(int64_t)r * k * fw + (int64_t)c * w + (f - r * fw)];
-  }
-}
-
-// unit weights: the weight sums the fold writes (a sequential fp32 count, which sticks at 2^24), for
-// a rank that folds no columns
-__global__ void k_wsum_offsets(int k, const int32_t* __restrict__ offsets, float* __restrict__ wsum,
-                               const int32_t* stop, int step_i) {
-  if (stopped(stop, step_i)) return;
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < k) wsum[c] = fminf((float)(offsets[c + 1] - offsets[c]), 16777216.f);
-}
-}  // namespace
-}  // namespace gdd
-
+// every rank runs the same replicated update: the same bits for every world size.
 extern "C" int gdd_lloyd_estep(int64_t n, int64_t r0, int64_t r1, int dim, const float* X, int k,
                                const float* C, const float* shift, int first, int32_t* labels,
                                void* state, int it, void* ws, size_t ws_bytes, gdd_stream_t stream) {
   GDD_REQUIRE(n > 0 && 0 <= r0 && r0 <= r1 && r1 <= n && dim > 0 && dim <= 512 && k > 0 && X && C &&
                   labels && state && ws && (first || shift) && it >= 0,
               "lloyd_estep: bad arguments");
-  hipStream_t s = to_hip(stream);
   LloydWs lw;
   if (!carve_lloyd(ws, ws_bytes, n, dim, k, &lw)) return fail(GDD_E_WORKSPACE, "lloyd_estep: workspace too small");
-  LloydState* st = static_cast<LloydState*>(state);
-  const int sa = 2 * it;
-  const int64_t m = r1 - r0;
-  if (m == 0) return GDD_OK;
-  const float* Xr = X + r0 * dim;
-  const bool prune = !forced("lloyd_no_prune") && lloyd_prune_ok(dim, k);
-  if (!prune) return kmeans_assign_dev(m, dim, Xr, k, C, lw.cn2, labels + r0, lw.keys, &st->stop_at, sa, s);
-  const double kappa = (2.0 * dim + 8.0) * kEps32;
-  if (first) {  // the rows' norms, once per fit (the bounds start at this E-step)
-    k_row_norm64<<<blocks_of(m, 64), 256, 0, s>>>(m, dim, Xr, lw.xn + r0);
-    GDD_LAUNCHED();
-  }
-  k_ham_centres<<<k + 1, 256, 0, s>>>(k, dim, C, shift, first ? 0 : 1, lw.sep, lw.glob, lw.count,
-                                      &st->stop_at, sa);
-  GDD_LAUNCHED();
-  if (!first) {
-    k_ham_test<<<blocks_of(m, 256 * kHamRows), 256, 0, s>>>(m, dim, labels + r0, lw.xn + r0, lw.ub + r0,
-                                                             lw.lb + r0, shift, lw.sep, lw.glob, kappa,
-                                                             lw.list, lw.count, &st->stop_at, sa);
-    GDD_LAUNCHED();
-  }
-  int rc = kmeans_assign_top2_dev(m, dim, Xr, first ? nullptr : lw.list, first ? nullptr : lw.count, k, C,
-                                  lw.cn2, lw.keys, lw.sec, &st->stop_at, sa, s);
-  if (rc) return rc;
-  const unsigned fgrid = std::min<unsigned>(blocks_of(m), 2048);
-  k_ham_finalize<<<fgrid, 256, 0, s>>>(lw.count, m, first ? nullptr : lw.list, lw.keys, lw.sec, lw.xn + r0,
-                                       lw.glob, kappa, labels + r0, lw.ub + r0, lw.lb + r0, &st->stop_at, sa);
-  GDD_LAUNCHED();
-  return GDD_OK;
+  if (r1 == r0) return GDD_OK;
+  const LloydStep a{n, dim, k, &lw, static_cast<LloydState*>(state), it, C};
+  return lloyd_estep_launch(a, X, r0, r1, labels, shift, first != 0, /*Xpad=*/nullptr, 0, lloyd_bounded(dim, k),
+                            /*norms_at_first=*/true, /*listlen=*/false, to_hip(stream));
 }
 
 extern "C" int gdd_lloyd_mstep(int64_t n, int dim, const float* X, const int32_t* labels, int k, int f0,
@@ -1694,28 +1726,12 @@ extern "C" int gdd_lloyd_mstep(int64_t n, int dim, const float* X, const int32_t
   GDD_REQUIRE(n > 0 && dim > 0 && k > 0 && 0 <= f0 && f0 <= f1 && f1 <= dim && X && labels && wsum &&
                   state && ws && (f0 == f1 || sums_cols) && it >= 0,
               "lloyd_mstep: bad arguments");
-  hipStream_t s = to_hip(stream);
   LloydWs lw;
   if (!carve_lloyd(ws, ws_bytes, n, dim, k, &lw)) return fail(GDD_E_WORKSPACE, "lloyd_mstep: workspace too small");
-  LloydState* st = static_cast<LloydState*>(state);
-  const int sa = 2 * it;
-  int rc = group_dev(n, labels, k, lw.perm, lw.offsets, lw.gws, lw.gb, &st->stop_at, sa, s);
-  if (rc) return rc;
-  if (f1 > f0) {
-    FoldArgs fa{f1 - f0, 0, 0, 0, 0, 0, 0, 0, X + f0, nullptr, lw.perm, lw.offsets, sums_cols, wsum,
-                nullptr, 0, &st->stop_at, sa, dim, n / k};
-    const double fs = forced_value("fold_slice", 1.5);
-    const double rows = fs * (double)n / (double)k;
-    fa.big_rows = fs > 0.0 ? (int)std::min<double>(std::max(rows, 4096.0), (double)INT_MAX) : 0;
-    rc = fold_launch(fa, k, false, s);
-    if (rc) return rc;
-  } else {
-    k_wsum_offsets<<<blocks_of(k), 256, 0, s>>>(k, lw.offsets, wsum, &st->stop_at, sa);
-    GDD_LAUNCHED();
-  }
-  k_lloyd_check_empty<<<1, 256, 0, s>>>(k, wsum, st, it, sa);
-  GDD_LAUNCHED();
-  return GDD_OK;
+  const LloydStep a{n, dim, k, &lw, static_cast<LloydState*>(state), it};
+  FoldArgs fa = fold_sums(n, k, dim, X, nullptr, lw.perm, lw.offsets, sums_cols, wsum).columns(f0, f1, dim);
+  if (f1 > f0) fa.big_rows = fold_big_rows(n, k);
+  return lloyd_mstep_launch(a, labels, fa, /*check_empty=*/true, to_hip(stream));
 }
 
 extern "C" int gdd_lloyd_update(int64_t n, int dim, int k, const float* parts, int fw, float* C_new,
@@ -1727,21 +1743,14 @@ extern "C" int gdd_lloyd_update(int64_t n, int dim, int k, const float* parts, i
               "lloyd_update: bad arguments");
   hipStream_t s = to_hip(stream);
   LloydState* st = static_cast<LloydState*>(state);
-  const int sb = 2 * it + 1;
   if (parts) {
     const int64_t total = (int64_t)k * dim;
     k_assemble_cols<<<(unsigned)std::min<int64_t>((total + 255) / 256, 2048), 256, 0, s>>>(
-        k, dim, fw, parts, C_new, &st->stop_at, sb);
+        k, dim, fw, parts, C_new, &st->stop_at, 2 * it + 1);
     GDD_LAUNCHED();
   }
-  k_avg_centers<<<k, 64, 0, s>>>(k, dim, C_new, wsum, C_old, shift, &st->stop_at, sb);
-  GDD_LAUNCHED();
-  const unsigned cgrid = std::min<unsigned>(blocks_of(n), 2048);
-  k_lloyd_changed<<<cgrid, 256, 0, s>>>(n, labels, labels_old, st, sb);
-  GDD_LAUNCHED();
-  k_lloyd_converge<<<1, 256, 0, s>>>(k, shift, tol, st, it, sb);
-  GDD_LAUNCHED();
-  return GDD_OK;
+  const LloydStep a{n, dim, k, nullptr, st, it, C_old};
+  return lloyd_update_launch(a, C_new, wsum, shift, tol, labels, labels_old, /*check_st=*/false, s);
 }
 
 // ---- the order-free fixed-point M-step (gdd.sharded.ShardedKMeans(mstep="reduce")) -----------------
@@ -1958,10 +1967,7 @@ __global__ __launch_bounds__(256) void k_reduce_check(int k, const long long* __
 // group_dev's workspace for any row count up to n (a rank groups its own rows; the tile plan, and
 // with it the histogram matrix, is not monotone in the row count)
 size_t reduce_group_ws(int64_t n, int k) {
-  Carver cv(nullptr, 0);
-  GroupWs g;
-  carve_count(cv, (int64_t)k * ((n + kTileUnit - 1) / kTileUnit), &g);  // the finest tiling's matrix
-  return std::max(group_ws(n, k), cv.off + 256);
+  return std::max(group_ws(n, k), group_ws(false, (int64_t)k * group_tiles(n, 1)));  // the finest tiling's matrix
 }
 
 // gdd_lloyd_reduce_local's buffers carved from ws (a null ws: measured); returns the workspace it needs
@@ -2017,9 +2023,6 @@ extern "C" int gdd_lloyd_reduce_local(int64_t n, int64_t r0, int64_t r1, int dim
   ReduceWs rw;
   if (ws_bytes < carve_reduce(ws, n, k, &rw))
     return fail(GDD_E_WORKSPACE, "lloyd_reduce_local: workspace too small");
-  int32_t *perm = rw.perm, *offsets = rw.offsets;
-  const size_t gb = rw.gb;
-  void* gws = rw.gws;
   LloydState* st = static_cast<LloydState*>(state);
   const int sa = 2 * it;
   long long* b64 = reinterpret_cast<long long*>(buf);
@@ -2027,9 +2030,9 @@ extern "C" int gdd_lloyd_reduce_local(int64_t n, int64_t r0, int64_t r1, int dim
   GDD_HIP(hipMemsetAsync(buf, 0, sizeof(int64_t) * gdd_lloyd_reduce_words(dim, k), s));
   const int64_t m = r1 - r0;
   if (m == 0) return GDD_OK;
-  int rc = group_dev(m, labels + r0, k, perm, offsets, gws, gb, &st->stop_at, sa, s);
+  int rc = group_dev(m, labels + r0, k, rw.perm, rw.offsets, rw.gws, rw.gb, &st->stop_at, sa, s);
   if (rc) return rc;
-  k_reduce_counts<<<blocks_of(k), 256, 0, s>>>(k, offsets, b64 + (int64_t)k * dim, &st->stop_at, sa);
+  k_reduce_counts<<<blocks_of(k), 256, 0, s>>>(k, rw.offsets, b64 + (int64_t)k * dim, &st->stop_at, sa);
   GDD_LAUNCHED();
   int G = 64;
   if (dim <= 32) {
@@ -2041,7 +2044,7 @@ extern "C" int gdd_lloyd_reduce_local(int64_t n, int64_t r0, int64_t r1, int dim
   const int ft = (int)forced_value("reduce_tile", 0.0);
   if (ft >= 64 && ft <= 16384 && (ft & (ft - 1)) == 0) tile = ft;  // a power of two >= 256 / G workers
   const dim3 grid(blocks_of(m, tile), (unsigned)((dim + 63) / 64));
-  k_reduce_sum<<<grid, 256, 0, s>>>(dim, X + r0 * dim, perm, offsets, k, exps, G, tile, b64, &st->stop_at, sa);
+  k_reduce_sum<<<grid, 256, 0, s>>>(dim, X + r0 * dim, rw.perm, rw.offsets, k, exps, G, tile, b64, &st->stop_at, sa);
   GDD_LAUNCHED();
   const unsigned cgrid = std::min<unsigned>(blocks_of(m), 2048);
   k_reduce_changed<<<cgrid, 256, 0, s>>>(m, labels + r0, labels_old + r0, b64 + (int64_t)k * dim + k,
@@ -2069,9 +2072,6 @@ extern "C" int gdd_lloyd_reduce_update(int dim, int k, const int64_t* buf, const
     k_reduce_check<<<1, 256, 0, s>>>(k, b64 + total, b64 + total + k, st, it, sb);
     GDD_LAUNCHED();
   }
-  k_avg_centers<<<k, 64, 0, s>>>(k, dim, C_new, wsum, C_old, shift, &st->stop_at, sb);
-  GDD_LAUNCHED();
-  k_lloyd_converge<<<1, 256, 0, s>>>(k, shift, tol, st, it, sb);
-  GDD_LAUNCHED();
-  return GDD_OK;
+  const LloydStep a{0, dim, k, nullptr, st, it, C_old};
+  return lloyd_update_launch(a, C_new, wsum, shift, tol, nullptr, nullptr, /*check_st=*/false, s);
 }

@@ -68,6 +68,17 @@ int sort_pairs_i32(const int32_t* keys_in, int32_t* keys_out, const int32_t* val
   return GDD_OK;
 }
 
+int sort_pairs_u32(const int32_t* keys_in, int32_t* keys_out, const int32_t* vals_in,
+                   int32_t* vals_out, int64_t n, void* ws, size_t ws_bytes, hipStream_t s) {
+  const uint32_t* kin = reinterpret_cast<const uint32_t*>(keys_in);
+  uint32_t* kout = reinterpret_cast<uint32_t*>(keys_out);
+  size_t need = 0;
+  GDD_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, kin, kout, vals_in, vals_out, (int)n, 0, 32, s));
+  if (need > ws_bytes) return fail(GDD_E_WORKSPACE, "sort workspace %zu < %zu", ws_bytes, need);
+  GDD_HIP(hipcub::DeviceRadixSort::SortPairs(ws, need, kin, kout, vals_in, vals_out, (int)n, 0, 32, s));
+  return GDD_OK;
+}
+
 // ---- launch-sequence replay --------------------------------------------------------------------
 namespace {
 // GDD_FORCE's token `name` (or `name=value`): its value text, nullptr if absent

@@ -76,9 +76,11 @@ SIGNATURES = {
     "gdd_rng_choice_unit_weights": (_c_int, [_vp, _c_i64, _vp]),
     "gdd_group_ws_bytes": (_c_size, [_c_i64, _c_int]),
     "gdd_group_by_label": (_c_int, [_c_i64, _vp, _c_int, _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_group_path": (ctypes.c_char_p, [_c_i64, _c_int]),
     "gdd_segment_sum_f32": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp]),
     "gdd_segment_sum_f32_part": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int,
                                           _vp, _vp, _vp]),
+    "gdd_fold_path": (ctypes.c_char_p, [_c_i64, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "gdd_average_centers": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "gdd_point_center_sqdist": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "gdd_relocate_distances": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _vp]),

@@ -267,6 +267,11 @@ int gdd_rng_choice_unit_weights(void* state, int64_t n, int64_t* out);
 size_t gdd_group_ws_bytes(int64_t n, int k);
 int gdd_group_by_label(int64_t n, const int32_t* labels, int k, int32_t* perm, int32_t* offsets,
                        void* ws, size_t ws_bytes, gdd_stream_t stream);
+/* the form that grouping takes under the current GDD_FORCE, by name (host only, no device call):      */
+/* small/m1|m2 (one workgroup, tiles of m x 1024 labels), count/m<m>/w<waves per block> (histograms,   */
+/* scan, scatter), radix (a pair sort on the labels); "invalid" for a shape gdd_group_by_label refuses. The string   */
+/* is the calling thread's until its next call.                                                        */
+const char* gdd_group_path(int64_t n, int k);
 
 /* Lloyd M-step accumulation, sklearn lloyd_iter_chunked_dense with one OpenMP thread                */
 /* (_k_means_lloyd.pyx:111-160, 208-213): sums[c,:] = sequential fp32 sum over the samples of c in    */
@@ -279,6 +284,23 @@ int gdd_segment_sum_f32(int64_t n, int dim, const float* X, const float* w, cons
 int gdd_segment_sum_f32_part(int64_t n, int dim, const float* X, const float* w, const int32_t* perm,
                              const int32_t* offsets, int k, int c0, int c1, float* sums_part,
                              float* wsum_part, gdd_stream_t stream);
+
+/* The kernel form an ordered fold takes, by name (host only, no device call): the Lloyd sums of n     */
+/* rows in k clusters over dim columns of rows of ld floats (0: dim) — gdd_segment_sum_f32, the Lloyd  */
+/* loop's M-step (over its zero-padded copy of X, dim % 4 != 0 from 65,536 rows on, dim is rounded up  */
+/* to a multiple of 4), a column range of gdd_lloyd_mstep (dim = f1 - f0, ld = the full dim) — or with */
+/* GDD_FOLD_MEAN the cluster means. flags say what the pointers would:                                 */
+#define GDD_FOLD_WEIGHTED 1    /* sample weights are given                                             */
+#define GDD_FOLD_MEAN 2        /* gdd_cluster_mean (fp64 chains); not with GDD_FOLD_WEIGHTED           */
+#define GDD_FOLD_X_UNALIGNED 4 /* X (at its first folded column) is not 16-byte aligned                */
+/* big_rows: clusters of at least that many members fold in 16-column slices where a chunk is wider    */
+/* (0: none, what every entry point but the Lloyd loop passes; < 0: the Lloyd loop's own rule under    */
+/* the current GDD_FORCE, 1.5 x n / k and at least 4096).                                              */
+/* cm/<columns>x<rows per chunk>[/sliced<rows per chunk of a sliced cluster>] (column-major chunks),   */
+/* seg/f32|mean/vec|scalar[/w][/small]/<column slices>x<rows per chunk>[/sliced<rows>] (row-major      */
+/* chunks; w: weighted, small: 8 KiB chunks for clusters of at most 64 rows on average); "invalid" for */
+/* n, dim or k below 1. The string is the calling thread's until its next call.                        */
+const char* gdd_fold_path(int64_t n, int dim, int ld, int k, int flags, int big_rows);
 
 /* sklearn _average_centers (_k_means_common.pyx:215-236): w>0: C[c,:] *= fp32(1.0/(double)w);       */
 /* w==0: C[c,:] = C[argmax(w),:] (first maximum; averaged already iff argmax < c, sklearn's loop     */

@@ -158,17 +158,48 @@ def test_average_centers_empty_cluster_copies_first_heaviest_in_loop_order():
     assert not np.array_equal(got[1], got[4])  # raw vs averaged copy
 
 
+# the form each grouping below means to run (gdd_group_path)
+GROUP_FORMS = {(1, 1): "small/m1", (1000, 3): "small/m1", (70000, 454): "count/m1/w4", (2500000, 196): "count/m3/w4",
+               (5000, 9000): "count/m1/w1", (6040, 604): "small/m1", (16384, 2048): "small/m1",
+               (16385, 1773): "small/m2", (32768, 1): "small/m2", (32768, 2047): "small/m2",
+               (17730, 1773): "small/m2", (3706, 371): "small/m1", (32769, 5): "count/m1/w4",
+               (5000, 4097): "count/m1/w1", (5000, 32769): "radix", (1048577, 7): "count/m2/w4"}
+
+
 @pytest.mark.parametrize("n,k", [(1, 1), (1000, 3), (70000, 454), (2500000, 196), (5000, 9000),
                                  # the one-workgroup form (n <= 32,768, k <= 2,048): both tile sizes,
                                  # odd k, the limits
                                  (6040, 604), (16384, 2048), (16385, 1773), (32768, 1), (32768, 2047),
-                                 (17730, 1773), (3706, 371)])
+                                 (17730, 1773), (3706, 371),
+                                 # the first counting shape, one wave per block, radix, two tile units
+                                 (32769, 5), (5000, 4097), (5000, 32769), (1048577, 7)])
 def test_group_by_label_is_a_stable_sort(n, k):
+    assert _lib.device_lib().gdd_group_path(n, k).decode() == GROUP_FORMS[n, k]
     rng = np.random.default_rng(n + k)
     lab = rng.integers(0, k, n).astype(np.int32)
     if n > 10:
         lab[::97] = -1  # outside [0, k): in no cluster
         lab[5::101] = k
+    perm, offs = gdd.group_by_label(torch.from_numpy(lab).cuda(), k)
+    valid = (lab >= 0) & (lab < k)
+    order = np.argsort(np.where(valid, lab, k), kind="stable")[: valid.sum()]
+    o = offs.cpu().numpy()
+    assert o[-1] == valid.sum()
+    assert np.array_equal(perm.cpu().numpy()[: valid.sum()], order.astype(np.int32))
+    assert np.array_equal(o[:-1], np.searchsorted(np.sort(lab[valid]), np.arange(k), side="left"))
+
+
+def test_group_radix_labels_outside_clusters():
+    """k > 32,768 (the radix form): labels outside [0, k) belong to no cluster whatever their low bits
+    -- negative ones whose low 16 bits name a cluster or are all ones, k itself, the largest int32 --
+    and perm lists the clusters' members first, in sample order."""
+    n, k = 5000, 32769
+    assert _lib.device_lib().gdd_group_path(n, k).decode() == "radix"
+    rng = np.random.default_rng(3)
+    lab = rng.integers(0, k, n).astype(np.int32)
+    for i, bad in enumerate([-1, -65536, -65536 + 7, -2 ** 31, k, k + 5, 65536, 2 ** 31 - 1]):
+        lab[i::53] = bad
+    lab[n - 1] = -1  # the last sorted key is outside
     perm, offs = gdd.group_by_label(torch.from_numpy(lab).cuda(), k)
     valid = (lab >= 0) & (lab < k)
     order = np.argsort(np.where(valid, lab, k), kind="stable")[: valid.sum()]

@@ -418,6 +418,9 @@ def test_kmeans_lloyd_sliced_fold_matches(monkeypatch, dim):
     fits = []
     for sl in ("1.5", "0"):
         force(monkeypatch, f"fold_slice={sl}")
+        path = _lib.device_lib().gdd_fold_path(len(X), dim, 0, k, 0, -1).decode()  # fewer than 65,536 rows: X itself
+        assert path == {("1.5", 47): "seg/f32/scalar/3x336/sliced1024", ("0", 47): "seg/f32/scalar/1x336",
+                        ("1.5", 48): "cm/48x336/sliced1024", ("0", 48): "cm/48x336"}[sl, dim]
         np.random.seed(15)
         fits.append(gdd.KMeans(n_clusters=k, n_init=1).fit(X))
     a, b = fits
@@ -450,6 +453,13 @@ def test_kmeans_lloyd_padded_fold_matches(monkeypatch, dim, prune):
     for pad, epad in (("1", "1"), ("1", "0"), ("0", "0")):
         force(monkeypatch, *([] if prune == "1" else ["lloyd_no_prune"]) + ([] if pad == "1" else ["fold_no_pad"]) +
               ([] if epad == "1" else ["estep_no_pad"]))
+        # the padded copy folds round4(dim) columns in 16-byte pieces, X itself one float at a time
+        lib = _lib.device_lib()
+        path = lib.gdd_fold_path(len(X), (dim + 3) // 4 * 4 if pad == "1" else dim, 0, k, 0, -1).decode()
+        if pad == "1":
+            assert path.startswith("cm/") or "/vec/" in path
+        else:
+            assert "/scalar/" in path
         np.random.seed(15)
         fits.append(gdd.KMeans(n_clusters=k, n_init=1).fit(X))
     a = fits[0]
