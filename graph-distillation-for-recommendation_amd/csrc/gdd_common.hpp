@@ -15,6 +15,8 @@
 #include <string>
 
 #include "gdd.h"
+#include "gdd_carve.hpp"
+#include "gdd_minibatch.hpp"
 
 namespace gdd {
 
@@ -41,26 +43,6 @@ int fail(int code, const char* fmt, ...);
 #define GDD_LAUNCHED() GDD_HIP(hipGetLastError())
 
 inline hipStream_t to_hip(gdd_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-// ---------------------------------------------------------------------------------------------
-// workspace carving: 256-byte aligned sub-allocations out of one caller buffer
-// ---------------------------------------------------------------------------------------------
-struct Carver {
-  char* base;
-  size_t cap;
-  size_t off = 0;
-  Carver(void* b, size_t c) : base(static_cast<char*>(b)), cap(c) {}
-  template <class T>
-  T* take(size_t count) {
-    off = (off + 255) & ~size_t(255);
-    T* p = reinterpret_cast<T*>(base ? base + off : nullptr);
-    off += count * sizeof(T);
-    return p;
-  }
-  bool ok() const { return off <= cap; }
-};
-// size-only variant used by the *_ws_bytes queries
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // ---------------------------------------------------------------------------------------------
 // device-wide exclusive scans (hipcub), declared here, defined in gdd_scan.hip
@@ -141,31 +123,66 @@ int replay_or_run(const char* site, const void* key, size_t key_bytes, hipStream
                   const std::function<int(hipStream_t)>& enqueue);
 
 // ---------------------------------------------------------------------------------------------
-// internal entry points of the device-resident MiniBatchKMeans loop (gdd_kmeans.hip, used by
-// gdd_fit.hip); DevMT / RngNext are defined in gdd_devrng.hpp
+// the MiniBatchKMeans step on the host (gdd_kmeans.hip; gdd_fit.hip drives it): one plan per shape,
+// one validate-and-carve helper, the launches over what it returns. RngNext: gdd_devrng.hpp.
+// DESIGN.md §4 (MiniBatch update, convergence, reassignment) has the path table.
 // ---------------------------------------------------------------------------------------------
-struct DevMT;
 struct RngNext;
-int minibatch_step_dev(int64_t b, int dim, const float* X, const int64_t* rows, int k,
-                       const float* C_old, float* C_new, float* weight_sums, int32_t* labels,
-                       int step_i, int64_t n_samples, int max_no_improvement, int flags,
-                       void* state, void* ws, size_t ws_bytes, const RngNext& rn, hipStream_t s);
-int mb_loop_begin(int64_t b, int k, void* ws, size_t ws_bytes, hipStream_t s);
-int mb_loop_end(int64_t b, int k, int last_step, int64_t n_samples, int max_no_improvement,
-                void* state, void* ws, size_t ws_bytes, hipStream_t s);
-int mb_rng_launch(const DevMT* in, DevMT* out, int64_t n, int64_t bs, int64_t* rows, hipStream_t s);
-// the device reassignment (k_mb_reassign): any k whose swap table fits the LDS; a step with more
-// than b/2 centres due (np.argsort's branch) is handed to the host through MBState.handoff
 constexpr size_t kReassignLdsCap = 150 * 1024;
-size_t mb_reassign_lds(int64_t bs, int k);
-bool mb_reassign_ok(int64_t bs, int k);
-int mb_reassign_launch(int step, int64_t bs, int dim, int k, float ratio, const float* X,
-                       const int64_t* rows, float* C_new, float* counts, void* step_ws,
-                       size_t step_ws_bytes, const DevMT* mt_in, DevMT* mt_mid, const RngNext& rn,
-                       void* state, hipStream_t s);
-// minibatch_step_dev flag: the step has no tail for step_i - 1 (the first step of a device segment
-// resumed after host steps, whose convergence tests the host already ran)
-constexpr int kStepNoTail = 1 << 16;
+constexpr int kRsParCopy = 2;  // k_mb_reassign: row copies in three block trips beside a one-wave next draw
+struct MbStepPlan {
+  bool ok;  // false: a shape the step refuses (b > kMaxBatch, dim > 512, a size <= 0)
+  int64_t b;
+  int dim, k;
+  int W, vec;      // k_mb_assign<W, vec>: waves (one 32-centre tile each) per block, 16-byte loads
+  int G, P, dimp;  // centre-tile groups x 32-point groups of blocks; dim rounded up to even
+  size_t assign_lds, update_lds;
+  // k_mb_reassign: the parallel copies (kRsParCopy) where their index tables (b/2 + 1 rows) fit after
+  // the swap table, else one dependent copy chain per reassigned cluster (0); -1: the swap table
+  // alone exceeds the LDS, and the fit takes the host loop
+  int rs_form;
+  size_t rs_lds;
+};
+// flags: GDD_STEP_PATH_UNALIGNED (what the pointers of a call would say)
+MbStepPlan mb_step_plan(int64_t b, int dim, int k, int flags);
+
+// Step s uses key buffer and distance buffer s % 2: the assignment writes keys[s%2], the update
+// reads them (and clears keys[(s+1)%2] for step s+1) and writes sq[s%2], the tail folds sq[s%2].
+struct StepWs {
+  unsigned long long* keys[2];
+  float* cn2;
+  float* sq[2];
+  float* inertia;
+};
+struct MbStep {  // what stays the same from step to step of a fit or a public call
+  MbStepPlan plan;
+  StepWs w;
+  MBState* st;
+  int64_t n_samples;
+  int max_ni;
+};
+// validates the shape and the workspace (errors as "<who>: ..."), plans and carves; X, C: for alignment
+int mb_step_open(const char* who, int64_t b, int dim, int k, int64_t n_samples, int max_no_improvement,
+                 const void* X, const void* C, void* state, void* ws, size_t ws_bytes, MbStep* out);
+// a host-driven step (gdd_minibatch_step): key fill, assignment, update, tail
+int mb_step_run(const MbStep& m, const float* X, const int64_t* rows, const float* C_old, float* C_new,
+                float* weight_sums, int32_t* labels, int step_i, int flags, hipStream_t s);
+// device loop, step s: the assignment launch also folds step s-1's inertia and runs its
+// convergence test (tail) and, with rn, draws batch s+1; the update clears the other key buffer
+int minibatch_step_dev(const MbStep& m, const float* X, const int64_t* rows, const float* C_old,
+                       float* C_new, float* weight_sums, int32_t* labels, int step_i, int flags,
+                       const RngNext& rn, hipStream_t s);
+// device loop: clear both key buffers before the first step; after the last step, its tail
+int mb_loop_begin(const MbStep& m, hipStream_t s);
+int mb_loop_end(const MbStep& m, int last_step, hipStream_t s);
+int mb_rng_launch(const DevMT* in, DevMT* out, int64_t n, int64_t bs, int64_t* rows, hipStream_t s);
+// the draw `rn` as a launch of device-loop step step_i (a no-op once the loop has stopped)
+int mb_rng_step_launch(const RngNext& rn, const int32_t* stop, int step_i, hipStream_t s);
+// the device reassignment (k_mb_reassign, plan.rs_form >= 0): a step with more than b/2 centres due
+// (np.argsort's branch) is handed to the host through MBState.handoff
+int mb_reassign_launch(const MbStep& m, int step, float ratio, const float* X, const int64_t* rows,
+                       float* C_new, float* counts, const DevMT* mt_in, DevMT* mt_mid,
+                       const RngNext& rn, hipStream_t s);
 
 // Bound of the LDS arrival-counter spins (k_mb_reassign, k-means++ speculative prefixes and draws):
 // a give-up takes the barrier redo. `make SPIN0=1` builds a twin with 0 so that every wait gives up

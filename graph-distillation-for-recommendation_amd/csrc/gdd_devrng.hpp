@@ -20,13 +20,9 @@
 #include <climits>
 #include <cstdint>
 
-namespace gdd {
+#include "gdd_rng.hpp"  // DevMT
 
-struct DevMT {  // key block + position, as gdd_mt_state without the gaussian cache
-  uint32_t key[624];
-  int32_t pos;
-  int32_t pad;
-};
+namespace gdd {
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
   y ^= (y >> 11);

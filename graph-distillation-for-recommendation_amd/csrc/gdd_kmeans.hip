@@ -1166,14 +1166,7 @@ __device__ __forceinline__ float fold_seq_lds(const float* __restrict__ b, int m
 // MiniBatchKMeans early stopping on the device: _mini_batch_convergence (_kmeans.py:1960-2027)
 // with Python-float (fp64, unfused) arithmetic, so the host need not read the inertia every step.
 // ---------------------------------------------------------------------------------------------
-struct MBState {
-  double ewa, ewa_min;
-  int32_t stop_at;       // offset 16: 0 while running, s+1 once the test fired at step s
-  int32_t has_ewa, has_min, no_improvement;
-  int32_t handoff;       // offset 32: s+1 once step s's reassignment needs the host (np.argsort branch)
-  int32_t pad[3];
-};
-
+// (MBState: gdd_minibatch.hpp)
 // one thread; st->stop_at is published with an agent-scope atomic store (read by sibling blocks).
 // The state is read into registers first (MbConv) — the tail block requests it before its inertia
 // fold, so the test after the fold costs no dependent memory trips; only this thread writes it.
@@ -2084,22 +2077,51 @@ extern "C" size_t gdd_minibatch_update_ws_bytes(int64_t b, int k) {
   return 256;  // member lists live in LDS; kept for ABI stability
 }
 
-namespace {
-constexpr int64_t kMaxBatch = 13312;  // 12*b bytes of LDS per update block (<= 156 KiB)
-
-size_t update_lds(int64_t b) {
+// ---- the MiniBatch step on the host: one plan, one launcher per kernel -------------------------------
+// (MiniBatch update, has the path table)
+static size_t update_lds(int64_t b) {
   // src rows (8b) + member positions (4b) + the new and the old centre rows (<= 2 x 512 floats)
   return 12 * (size_t)b + 2 * 512 * sizeof(float);
 }
 
-int launch_update(int64_t b, int dim, const float* X, const int64_t* rows, const float* w,
+MbStepPlan gdd::mb_step_plan(int64_t b, int dim, int k, int flags) {
+  MbStepPlan p{};
+  p.b = b, p.dim = dim, p.k = k;
+  if (b <= 0 || dim <= 0 || k <= 0) return p;
+  p.ok = b <= kMaxBatch && dim <= 512;
+  // four waves while their tiles leave room for a second block per CU, two while they fit at all
+  p.W = mb_assign_lds(4, dim) <= 96 * 1024 ? 4 : mb_assign_lds(2, dim) <= kLdsCap ? 2 : 1;
+  p.vec = dim % 4 == 0 && !(flags & GDD_STEP_PATH_UNALIGNED);
+  p.dimp = (dim + 1) & ~1;
+  p.G = ((k + 31) / 32 + p.W - 1) / p.W;
+  p.P = (int)((b + 31) / 32);
+  // the tiles, or what the extra workgroups stage: the tail's 2048 distances, the draw's key ring
+  p.assign_lds = std::max({mb_assign_lds(p.W, dim), sizeof(float) * 2048 + 16, kMtRingBytes + 64});
+  p.update_lds = update_lds(b);
+  // the swap table: b shuffle draws (an even count), the reassigned clusters, the draw's key ring
+  const size_t base = sizeof(int) * (size_t)((b + 1) & ~1ll) + sizeof(int) * (size_t)k + kMtRingBytes;
+  const size_t par = ((base + 7) & ~(size_t)7) + 12 * (size_t)(b / 2 + 1);  // m <= b/2 sources, positions
+  p.rs_form = base > kReassignLdsCap ? -1 : par <= kReassignLdsCap ? kRsParCopy : 0;
+  p.rs_lds = p.rs_form == kRsParCopy ? par : base;
+  return p;
+}
+
+extern "C" const char* gdd_minibatch_step_path(int64_t b, int dim, int k, int flags) {
+  static thread_local char name[32];
+  const MbStepPlan p = mb_step_plan(b, dim, k, flags);
+  if (!p.ok) return "invalid";
+  snprintf(name, sizeof name, "w%d/%s/g%dxp%d", p.W, p.vec ? "vec" : "scalar", p.G, p.P);
+  return name;
+}
+
+namespace {
+int launch_update(size_t lds, int64_t b, int dim, const float* X, const int64_t* rows, const float* w,
                   const int32_t* labels, const unsigned long long* keys, int k, const float* C_old,
                   float* C_new, float* Wsum, float* cn2_out, const int32_t* stop, int step_i,
                   int32_t* labels_out, float* sq_out, unsigned long long* keys_reset,
                   hipStream_t s) {
   GDD_REQUIRE(b <= kMaxBatch, "minibatch: batch %lld exceeds %lld", (long long)b,
               (long long)kMaxBatch);
-  const size_t lds = update_lds(b);
   if (const int rc = lds_opt_in((const void*)k_minibatch_update, lds)) return rc;
   k_minibatch_update<<<k, 64, lds, s>>>(b, dim, X, rows, w, labels, keys, k, C_old, C_new, Wsum,
                                         cn2_out, stop, step_i, labels_out, sq_out, keys_reset);
@@ -2107,44 +2129,30 @@ int launch_update(int64_t b, int dim, const float* X, const int64_t* rows, const
   return GDD_OK;
 }
 
-template <int W, bool VEC>
-int launch_mb_assign_t(int64_t b, int dim, const float* X, const int64_t* rows, int k,
-                       const float* C, const float* cn2, unsigned long long* keys,
-                       const int32_t* stop, int step_i, const MbTail& tl, const RngNext& rn,
-                       hipStream_t s) {
-  const int dimp = (dim + 1) & ~1;
-  const int tiles = (k + 31) / 32;
-  const int G = (tiles + W - 1) / W;
-  const int P = (int)((b + 31) / 32);
-  const size_t lds = std::max({mb_assign_lds(W, dim), sizeof(float) * 2048 + 16,
-                               kMtRingBytes + 64});
-  if (const int rc = lds_opt_in((const void*)k_mb_assign<W, VEC>, lds)) return rc;
-  const unsigned grid = (unsigned)(P * G) + (tl.active ? 1u : 0u) + (rn.rows ? 1u : 0u);
-  k_mb_assign<W, VEC><<<grid, 64 * W, lds, s>>>(b, dim, dimp, X, rows, k, C, cn2, keys, G, P, stop,
-                                                step_i, tl, rn);
+struct MbAssignArgs {
+  const float* X;
+  const int64_t* rows;
+  const float* C;
+  const float* cn2;
+  unsigned long long* keys;
+  const int32_t* stop;
+  int step_i;
+  MbTail tl;   // active: one more workgroup runs the previous step's tail
+  RngNext rn;  // rows: one more workgroup draws the next batch
+};
+
+int mb_assign_launch(const MbStepPlan& p, const MbAssignArgs& a, hipStream_t s) {
+  using Fn = decltype(&k_mb_assign<4, true>);
+  static const Fn table[3][2] = {{k_mb_assign<1, false>, k_mb_assign<1, true>},
+                                 {k_mb_assign<2, false>, k_mb_assign<2, true>},
+                                 {k_mb_assign<4, false>, k_mb_assign<4, true>}};
+  const Fn fn = table[p.W >> 1][p.vec];
+  if (const int rc = lds_opt_in((const void*)fn, p.assign_lds)) return rc;
+  const unsigned grid = (unsigned)(p.P * p.G) + (a.tl.active ? 1u : 0u) + (a.rn.rows ? 1u : 0u);
+  fn<<<grid, 64 * p.W, p.assign_lds, s>>>(p.b, p.dim, p.dimp, a.X, a.rows, p.k, a.C, a.cn2, a.keys, p.G,
+                                          p.P, a.stop, a.step_i, a.tl, a.rn);
   GDD_LAUNCHED();
   return GDD_OK;
-}
-
-template <bool VEC>
-int launch_mb_assign_v(int64_t b, int dim, const float* X, const int64_t* rows, int k,
-                       const float* C, const float* cn2, unsigned long long* keys,
-                       const int32_t* stop, int step_i, const MbTail& tl, const RngNext& rn,
-                       hipStream_t s) {
-  if (mb_assign_lds(4, dim) <= 96 * 1024)
-    return launch_mb_assign_t<4, VEC>(b, dim, X, rows, k, C, cn2, keys, stop, step_i, tl, rn, s);
-  if (mb_assign_lds(2, dim) <= kLdsCap)
-    return launch_mb_assign_t<2, VEC>(b, dim, X, rows, k, C, cn2, keys, stop, step_i, tl, rn, s);
-  return launch_mb_assign_t<1, VEC>(b, dim, X, rows, k, C, cn2, keys, stop, step_i, tl, rn, s);
-}
-
-int launch_mb_assign(int64_t b, int dim, const float* X, const int64_t* rows, int k, const float* C,
-                     const float* cn2, unsigned long long* keys, const int32_t* stop, int step_i,
-                     const MbTail& tl, const RngNext& rn, hipStream_t s) {
-  const bool vec = (dim % 4 == 0) &&
-                   ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(C)) & 15) == 0;
-  return vec ? launch_mb_assign_v<true>(b, dim, X, rows, k, C, cn2, keys, stop, step_i, tl, rn, s)
-             : launch_mb_assign_v<false>(b, dim, X, rows, k, C, cn2, keys, stop, step_i, tl, rn, s);
 }
 }  // namespace
 
@@ -2157,20 +2165,12 @@ extern "C" int gdd_minibatch_update(int64_t b, int dim, const float* X, const in
   GDD_REQUIRE(C_old != C_new, "minibatch_update: C_old and C_new must differ");
   (void)ws;
   (void)ws_bytes;
-  return launch_update(b, dim, X, rows, w, labels, nullptr, k, C_old, C_new, weight_sums, nullptr,
+  return launch_update(update_lds(b), b, dim, X, rows, w, labels, nullptr, k, C_old, C_new, weight_sums, nullptr,
                        nullptr, 0, nullptr, nullptr, nullptr, to_hip(stream));
 }
 
 // ---- fused MiniBatchKMeans step (_mini_batch_step + _mini_batch_convergence) ------------------
-// Step s uses key buffer and distance buffer s % 2: the assignment writes keys[s%2], the update
-// reads them (and clears keys[(s+1)%2] for step s+1) and writes sq[s%2], the tail folds sq[s%2].
 namespace {
-struct StepWs {
-  unsigned long long* keys[2];
-  float* cn2;
-  float* sq[2];
-  float* inertia;
-};
 // the step's buffers carved from ws; with a null ws only measured (*bytes: the workspace they need)
 StepWs carve_step(void* ws, size_t ws_bytes, int64_t b, int k, size_t* bytes = nullptr) {
   Carver cv(ws, ws_bytes);
@@ -2194,82 +2194,86 @@ extern "C" size_t gdd_minibatch_step_ws_bytes(int64_t b, int k) {
   return bytes;
 }
 
-extern "C" int gdd_minibatch_step(int64_t b, int dim, const float* X, const int64_t* rows, int k,
-                                  const float* C_old, float* C_new, float* weight_sums,
-                                  int32_t* labels, int step_i, int64_t n_samples,
-                                  int max_no_improvement, int flags, void* state, void* ws,
-                                  size_t ws_bytes, gdd_stream_t stream) {
-  GDD_REQUIRE(b > 0 && dim > 0 && dim <= 512 && k > 0 && n_samples > 0, "minibatch_step: bad shape");
-  GDD_REQUIRE(X && rows && C_old && C_new && weight_sums && labels && state && ws,
-              "minibatch_step: null pointer");
-  GDD_REQUIRE(C_old != C_new, "minibatch_step: C_old and C_new must differ");
-  if (ws_bytes < gdd_minibatch_step_ws_bytes(b, k))
-    return fail(GDD_E_WORKSPACE, "minibatch_step: workspace too small");
-  hipStream_t s = to_hip(stream);
-  MBState* st = static_cast<MBState*>(state);
-  const int32_t* stop = &st->stop_at;
-  StepWs w = carve_step(ws, ws_bytes, b, k);
+int gdd::mb_step_open(const char* who, int64_t b, int dim, int k, int64_t n_samples,
+                      int max_no_improvement, const void* X, const void* C, void* state, void* ws,
+                      size_t ws_bytes, MbStep* out) {
+  GDD_REQUIRE(b > 0 && dim > 0 && dim <= 512 && k > 0 && n_samples > 0, "%s: bad shape", who);
+  GDD_REQUIRE(state && ws, "%s: null pointer", who);
+  if (ws_bytes < gdd_minibatch_step_ws_bytes(b, k)) return fail(GDD_E_WORKSPACE, "%s: workspace too small", who);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(C)) & 15) == 0;
+  *out = MbStep{mb_step_plan(b, dim, k, aligned ? 0 : GDD_STEP_PATH_UNALIGNED), carve_step(ws, ws_bytes, b, k),
+                static_cast<MBState*>(state), n_samples, max_no_improvement};
+  return GDD_OK;
+}
+
+int gdd::mb_step_run(const MbStep& m, const float* X, const int64_t* rows, const float* C_old, float* C_new,
+                     float* weight_sums, int32_t* labels, int step_i, int flags, hipStream_t s) {
+  const MbStepPlan& p = m.plan;
+  const StepWs& w = m.w;
+  const int32_t* stop = &m.st->stop_at;
   const int cur = step_i & 1;
-  k_fill_u64<<<blocks_for(b), 256, 0, s>>>(b, w.keys[cur], ~0ull, stop, step_i);
+  k_fill_u64<<<blocks_for(p.b), 256, 0, s>>>(p.b, w.keys[cur], ~0ull, stop, step_i);
   GDD_LAUNCHED();
   const float* cn2 = (flags & GDD_STEP_NORMS_VALID) ? w.cn2 : nullptr;
-  const MbTail none{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-  int rc = launch_mb_assign(b, dim, X, rows, k, C_old, cn2, w.keys[cur], stop, step_i, none,
-                            RngNext{nullptr, nullptr, nullptr, 0, 0}, s);
+  int rc = mb_assign_launch(p, MbAssignArgs{X, rows, C_old, cn2, w.keys[cur], stop, step_i, MbTail{}, RngNext{}}, s);
   if (rc) return rc;
-  rc = launch_update(b, dim, X, rows, nullptr, nullptr, w.keys[cur], k, C_old, C_new, weight_sums,
-                     w.cn2, stop, step_i, labels, w.sq[cur], nullptr, s);
+  rc = launch_update(p.update_lds, p.b, p.dim, X, rows, nullptr, nullptr, w.keys[cur], p.k, C_old, C_new,
+                     weight_sums, w.cn2, stop, step_i, labels, w.sq[cur], nullptr, s);
   if (rc) return rc;
-  const MbTail tl{w.sq[cur], w.inertia, st, b, n_samples, max_no_improvement, step_i,
+  const MbTail tl{w.sq[cur], w.inertia, m.st, p.b, m.n_samples, m.max_ni, step_i,
                   (flags & GDD_STEP_CONVERGE) ? 1 : 0, 1};
   k_mb_tail<<<1, 256, 0, s>>>(tl, stop);
   GDD_LAUNCHED();
   return GDD_OK;
 }
 
-// device loop, step s: the assignment launch also folds step s-1's inertia and runs its
-// convergence test (tail) and, with rn, draws batch s+1; the update clears the other key buffer
-int gdd::minibatch_step_dev(int64_t b, int dim, const float* X, const int64_t* rows, int k,
-                            const float* C_old, float* C_new, float* weight_sums, int32_t* labels,
-                            int step_i, int64_t n_samples, int max_no_improvement, int flags,
-                            void* state, void* ws, size_t ws_bytes, const RngNext& rn,
-                            hipStream_t s) {
-  GDD_REQUIRE(b > 0 && dim > 0 && dim <= 512 && k > 0 && n_samples > 0, "minibatch_step: bad shape");
-  GDD_REQUIRE(X && rows && C_old && C_new && weight_sums && labels && state && ws,
-              "minibatch_step: null pointer");
+extern "C" int gdd_minibatch_step(int64_t b, int dim, const float* X, const int64_t* rows, int k,
+                                  const float* C_old, float* C_new, float* weight_sums,
+                                  int32_t* labels, int step_i, int64_t n_samples,
+                                  int max_no_improvement, int flags, void* state, void* ws,
+                                  size_t ws_bytes, gdd_stream_t stream) {
+  MbStep m;
+  if (const int rc = mb_step_open("minibatch_step", b, dim, k, n_samples, max_no_improvement, X, C_old, state,
+                                  ws, ws_bytes, &m))
+    return rc;
+  GDD_REQUIRE(X && rows && C_old && C_new && weight_sums && labels, "minibatch_step: null pointer");
   GDD_REQUIRE(C_old != C_new, "minibatch_step: C_old and C_new must differ");
-  if (ws_bytes < gdd_minibatch_step_ws_bytes(b, k))
-    return fail(GDD_E_WORKSPACE, "minibatch_step: workspace too small");
-  MBState* st = static_cast<MBState*>(state);
-  const int32_t* stop = &st->stop_at;
-  StepWs w = carve_step(ws, ws_bytes, b, k);
+  return mb_step_run(m, X, rows, C_old, C_new, weight_sums, labels, step_i, flags, to_hip(stream));
+}
+
+int gdd::minibatch_step_dev(const MbStep& m, const float* X, const int64_t* rows, const float* C_old,
+                            float* C_new, float* weight_sums, int32_t* labels, int step_i, int flags,
+                            const RngNext& rn, hipStream_t s) {
+  const MbStepPlan& p = m.plan;
+  const StepWs& w = m.w;
+  const int32_t* stop = &m.st->stop_at;
   const int cur = step_i & 1, prev = cur ^ 1;
   const float* cn2 = (flags & GDD_STEP_NORMS_VALID) ? w.cn2 : nullptr;
-  const MbTail tl{w.sq[prev], w.inertia, st, b, n_samples, max_no_improvement, step_i - 1,
+  const MbTail tl{w.sq[prev], w.inertia, m.st, p.b, m.n_samples, m.max_ni, step_i - 1,
                   (flags & GDD_STEP_CONVERGE) ? 1 : 0, (step_i > 0 && !(flags & kStepNoTail)) ? 1 : 0};
-  int rc = launch_mb_assign(b, dim, X, rows, k, C_old, cn2, w.keys[cur], stop, step_i, tl, rn, s);
+  // the draw's workgroup needs at least 256 threads (mt_randint_ring): the two- and one-wave forms
+  // draw in a launch of their own
+  const bool own_draw = rn.rows && p.W < 4;
+  if (own_draw)
+    if (const int rc = mb_rng_step_launch(rn, stop, step_i, s)) return rc;
+  int rc = mb_assign_launch(
+      p, MbAssignArgs{X, rows, C_old, cn2, w.keys[cur], stop, step_i, tl, own_draw ? RngNext{} : rn}, s);
   if (rc) return rc;
-  return launch_update(b, dim, X, rows, nullptr, nullptr, w.keys[cur], k, C_old, C_new,
+  return launch_update(p.update_lds, p.b, p.dim, X, rows, nullptr, nullptr, w.keys[cur], p.k, C_old, C_new,
                        weight_sums, w.cn2, stop, step_i, labels, w.sq[cur], w.keys[prev], s);
 }
 
-// device loop: clear both key buffers before step 0; after the last step, its tail
-int gdd::mb_loop_begin(int64_t b, int k, void* ws, size_t ws_bytes, hipStream_t s) {
-  StepWs w = carve_step(ws, ws_bytes, b, k);
+int gdd::mb_loop_begin(const MbStep& m, hipStream_t s) {
   for (int q = 0; q < 2; ++q) {
-    k_fill_u64<<<blocks_for(b), 256, 0, s>>>(b, w.keys[q], ~0ull, nullptr, 0);
+    k_fill_u64<<<blocks_for(m.plan.b), 256, 0, s>>>(m.plan.b, m.w.keys[q], ~0ull, nullptr, 0);
     GDD_LAUNCHED();
   }
   return GDD_OK;
 }
 
-int gdd::mb_loop_end(int64_t b, int k, int last_step, int64_t n_samples, int max_no_improvement,
-                     void* state, void* ws, size_t ws_bytes, hipStream_t s) {
-  StepWs w = carve_step(ws, ws_bytes, b, k);
-  MBState* st = static_cast<MBState*>(state);
-  const MbTail tl{w.sq[last_step & 1], w.inertia, st, b, n_samples, max_no_improvement, last_step,
-                  1, 1};
-  k_mb_tail<<<1, 256, 0, s>>>(tl, &st->stop_at);
+int gdd::mb_loop_end(const MbStep& m, int last_step, hipStream_t s) {
+  const MbTail tl{m.w.sq[last_step & 1], m.w.inertia, m.st, m.plan.b, m.n_samples, m.max_ni, last_step, 1, 1};
+  k_mb_tail<<<1, 256, 0, s>>>(tl, &m.st->stop_at);
   GDD_LAUNCHED();
   return GDD_OK;
 }
@@ -2277,13 +2281,12 @@ int gdd::mb_loop_end(int64_t b, int k, int last_step, int64_t n_samples, int max
 extern "C" int gdd_minibatch_converge(int64_t b, int k, int step_i, int64_t n_samples,
                                       int max_no_improvement, void* state, void* ws,
                                       size_t ws_bytes, gdd_stream_t stream) {
-  GDD_REQUIRE(b > 0 && k > 0 && n_samples > 0 && state && ws, "minibatch_converge: bad arguments");
-  if (ws_bytes < gdd_minibatch_step_ws_bytes(b, k))
-    return fail(GDD_E_WORKSPACE, "minibatch_converge: workspace too small");
+  MbStep m;  // no launch here depends on dim
+  if (const int rc = mb_step_open("minibatch_converge", b, 1, k, n_samples, max_no_improvement, nullptr, nullptr,
+                                  state, ws, ws_bytes, &m))
+    return rc;
   // the batch inertia of the preceding gdd_minibatch_step, at its fixed workspace offset
-  StepWs w = carve_step(ws, ws_bytes, b, k);
-  k_mb_converge<<<1, 64, 0, to_hip(stream)>>>(step_i, b, n_samples, max_no_improvement, w.inertia,
-                                              static_cast<MBState*>(state));
+  k_mb_converge<<<1, 64, 0, to_hip(stream)>>>(step_i, b, n_samples, max_no_improvement, m.w.inertia, m.st);
   GDD_LAUNCHED();
   return GDD_OK;
 }
@@ -2315,7 +2318,13 @@ __global__ __launch_bounds__(1024) void k_mb_rng(const DevMT* __restrict__ in, D
   mt_randint_from(in, ring, 0, n, bs, rows, out);
 }
 
-constexpr int kRsParCopy = 2;  // k_mb_reassign: row copies in three block trips beside a one-wave next draw
+// the same draw as a launch of a device-loop step (the assignment forms of fewer than four waves,
+// whose extra workgroup is too small for it): nothing once the loop has stopped
+__global__ __launch_bounds__(1024) void k_mb_rng_step(RngNext rn, const int32_t* __restrict__ stop, int step_i) {
+  __shared__ uint32_t ring[kMtRingBytes / sizeof(uint32_t)];
+  if (stopped(stop, step_i)) return;
+  mt_randint_from(rn.in, ring, 0, rn.n, rn.bs, rn.rows, rn.out);
+}
 
 // LDS arrival counters among some of a workgroup's waves (the others busy elsewhere): every
 // arriving wave's earlier LDS and global writes are visible to a wave whose wait returned true;
@@ -2558,32 +2567,20 @@ int mb_rng_launch(const DevMT* in, DevMT* out, int64_t n, int64_t bs, int64_t* r
   return GDD_OK;
 }
 
-size_t mb_reassign_lds(int64_t bs, int k) {
-  return sizeof(int) * (size_t)((bs + 1) & ~1ll) + sizeof(int) * (size_t)k + kMtRingBytes;
+int mb_rng_step_launch(const RngNext& rn, const int32_t* stop, int step_i, hipStream_t s) {
+  k_mb_rng_step<<<1, 1024, 0, s>>>(rn, stop, step_i);
+  GDD_LAUNCHED();
+  return GDD_OK;
 }
 
-bool mb_reassign_ok(int64_t bs, int k) { return mb_reassign_lds(bs, k) <= kReassignLdsCap; }
-
-int mb_reassign_launch(int step, int64_t bs, int dim, int k, float ratio, const float* X,
-                       const int64_t* rows, float* C_new, float* counts, void* step_ws,
-                       size_t step_ws_bytes, const DevMT* mt_in, DevMT* mt_mid, const RngNext& rn,
-                       void* state, hipStream_t s) {
-  StepWs w = carve_step(step_ws, step_ws_bytes, bs, k);
-  size_t lds = mb_reassign_lds(bs, k);
-  GDD_REQUIRE(lds <= kReassignLdsCap, "mb_reassign: batch too large for the LDS swap table");
-  // the parallel copies (kRsParCopy) where their index tables (bs/2 + 1 rows: m <= bs/2 here) fit
-  // after the base layout; else one dependent copy chain per reassigned cluster
-  int form = kRsParCopy;
-  const size_t par_lds =
-      ((sizeof(int) * (size_t)(((bs + 1) & ~1ll) + k) + kMtRingBytes + 7) & ~(size_t)7) +
-      12 * (size_t)(bs / 2 + 1);
-  if ((form & kRsParCopy) && par_lds <= kReassignLdsCap)
-    lds = std::max(lds, par_lds);
-  else
-    form &= ~kRsParCopy;
-  if (const int rc = lds_opt_in((const void*)k_mb_reassign, lds)) return rc;
-  k_mb_reassign<<<1, 1024, lds, s>>>(step, bs, dim, k, ratio, X, rows, C_new, counts, w.cn2, mt_in,
-                                     mt_mid, rn, static_cast<MBState*>(state), form);
+int mb_reassign_launch(const MbStep& m, int step, float ratio, const float* X, const int64_t* rows,
+                       float* C_new, float* counts, const DevMT* mt_in, DevMT* mt_mid,
+                       const RngNext& rn, hipStream_t s) {
+  const MbStepPlan& p = m.plan;
+  GDD_REQUIRE(p.rs_form >= 0, "mb_reassign: batch too large for the LDS swap table");
+  if (const int rc = lds_opt_in((const void*)k_mb_reassign, p.rs_lds)) return rc;
+  k_mb_reassign<<<1, 1024, p.rs_lds, s>>>(step, p.b, p.dim, p.k, ratio, X, rows, C_new, counts, m.w.cn2, mt_in,
+                                          mt_mid, rn, m.st, p.rs_form);
   GDD_LAUNCHED();
   return GDD_OK;
 }

@@ -26,6 +26,13 @@ struct MTState {  // layout of gdd_mt_state in gdd.h
   double gauss;
 };
 
+struct DevMT {  // the device loops' state: key block + position, gdd_mt_state without the gaussian cache
+  uint32_t key[624];
+  int32_t pos;
+  int32_t pad;
+};
+static_assert(sizeof(DevMT) == 624 * 4 + 8, "DevMT layout");
+
 class LegacyRNG {
  public:
   explicit LegacyRNG(MTState* s) : s_(s) {}

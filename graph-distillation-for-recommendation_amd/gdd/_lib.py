@@ -65,11 +65,15 @@ SIGNATURES = {
                                     _c_i64, _c_int, _c_int, _vp, _vp, _c_size, _vp]),
     "gdd_minibatch_converge": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_int, _vp, _vp, _c_size,
                                         _vp]),
+    "gdd_minibatch_step_path": (ctypes.c_char_p, [_c_i64, _c_int, _c_int, _c_int]),
     "gdd_minibatch_kmeans_fit_ws_bytes": (_c_size, [_c_i64, _c_int, _c_int, _c_i64, _c_i64]),
     "gdd_minibatch_kmeans_fit": (_c_int, [_c_i64, _c_int, _vp, _c_int, _c_i64, _c_int, _c_int,
                                           _c_f32, _c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _c_size, _vp, _c_size, _vp]),
     "gdd_minibatch_kmeans_fit_host_ws_bytes": (_c_size, [_c_i64, _c_int, _c_i64, _c_i64]),
+    "gdd_minibatch_fit_path": (ctypes.c_char_p, [_c_i64, _c_int, _c_int, _c_i64]),
+    "gdd_minibatch_schedule": (_c_int, [_c_i64, _c_i64, _c_int, _c_i64, _c_int, _c_i64, _c_f32, _c_i64, _vp]),
+    "gdd_minibatch_reassign_host": (_c_int, [_vp, _c_int, _c_i64, _c_f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdd_rng_randint": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp]),
     "gdd_rng_random_sample": (_c_int, [_vp, _c_i64, _vp]),
     "gdd_rng_permutation": (_c_int, [_vp, _c_i64, _vp]),
@@ -190,6 +194,10 @@ def load() -> ctypes.CDLL:
             f"libgdd.so not found at {LIB_PATH}: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f"{LIB_PATH} is an older build of libgdd.so: it lacks {', '.join(missing)}. "
+                           "Rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`.")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res

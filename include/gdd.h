@@ -222,6 +222,12 @@ int gdd_minibatch_step(int64_t b, int dim, const float* X, const int64_t* rows, 
                        void* state, void* ws, size_t ws_bytes, gdd_stream_t stream);
 int gdd_minibatch_converge(int64_t b, int k, int step_i, int64_t n_samples, int max_no_improvement,
                            void* state, void* ws, size_t ws_bytes, gdd_stream_t stream);
+/* The form a step's launches take, by name (host only, no device call): w<waves per assignment block:  */
+/* 4, 2 or 1 by the LDS a dim needs>/vec|scalar (16-byte loads: dim % 4 == 0 and aligned X and C)/       */
+/* g<centre-tile groups>xp<32-point groups> (the assignment's grid); "invalid" for a shape the step      */
+/* refuses (b > 13312, dim > 512, a size <= 0). The string is the calling thread's until its next call.   */
+#define GDD_STEP_PATH_UNALIGNED 1 /* X or C is not 16-byte aligned                                       */
+const char* gdd_minibatch_step_path(int64_t b, int dim, int k, int flags);
 
 /* numpy legacy RandomState state: ('MT19937', key[624], pos, has_gauss, cached_gaussian).          */
 typedef struct gdd_mt_state {
@@ -237,7 +243,11 @@ typedef struct gdd_mt_state {
 /* and (compute_labels) the final labels pass + inertia. `rng` is the caller's RandomState, advanced */
 /* exactly as scikit-learn advances it. argsort_cb must reproduce np.argsort(weight_sums); it is    */
 /* only called when more than batch/2 centres are due for reassignment (possible only if k > b/2).   */
-/* Host syncs: one per reassignment step and one at the end. centers_out k x dim, labels_out n,      */
+/* Host syncs: the step loop is device-resident (draws, reassignments and the convergence test run   */
+/* there), so the host waits once per 16-step chunk, for the chunk before the one just enqueued, and  */
+/* once at the end; only a step whose reassignment needs np.argsort (more than batch/2 centres due)   */
+/* and the steps after it while a weight sum is zero run host-driven, with one sync per reassignment. */
+/* centers_out k x dim, labels_out n,                                                                */
 /* inertia_out (device): compute_labels 1 -> 1 float, the inertia; compute_labels 2 -> n floats, the  */
 /* per-sample squared distances (the caller folds them, e.g. on a side stream); n_steps_out, ewa_out  */
 /* (nullable) host.                                                                                  */
@@ -252,6 +262,29 @@ int gdd_minibatch_kmeans_fit(int64_t n, int dim, const float* X, int k, int64_t 
                              size_t host_ws_bytes, gdd_stream_t stream);
 /* pinned host staging the fit needs (host_ws: page-locked, caller-owned, e.g. a pinned torch tensor) */
 size_t gdd_minibatch_kmeans_fit_host_ws_bytes(int64_t n, int k, int64_t batch_size, int64_t init_size);
+/* The loop a fit takes, by name (host only, no device call): dev/par or dev/chain, the device-resident */
+/* loop with the reassignment kernel's parallel row copies or, where their index tables do not fit    */
+/* the LDS, one copy chain per reassigned cluster; host, the host-driven loop (GDD_HOST_LOOP set, or   */
+/* the reassignment's swap table exceeds the LDS); "invalid" for a shape the fit refuses.              */
+const char* gdd_minibatch_fit_path(int64_t n, int dim, int k, int64_t batch_size);
+/* The device loop's schedule of steps [i0, i0 + m) of a segment that starts at step i0 (host only; for */
+/* tests): rr_base the last reassignment step, norms_valid0 whether the workspace norms match step     */
+/* i0's centres. out[j] describes step i0 + j: GDD_SCHED_* bits, then the indices of its C_old (bit 4), */
+/* its rows buffer (bit 5) and its generator slot (bits 6-7).                                          */
+#define GDD_SCHED_REASSIGN 1    /* the reassignment launch follows the update                          */
+#define GDD_SCHED_HAS_NEXT 2    /* the step draws the next batch                                       */
+#define GDD_SCHED_NORMS_VALID 4 /* GDD_STEP_NORMS_VALID                                                */
+#define GDD_SCHED_NO_TAIL 8     /* no tail for the step before (the host ran its convergence test)     */
+int gdd_minibatch_schedule(int64_t i0, int64_t rr_base, int norms_valid0, int64_t n_steps, int k,
+                           int64_t batch_size, float reassignment_ratio, int64_t m, int32_t* out);
+/* The host loop's reassignment decision (_mini_batch_step's branch, numpy float32 semantics; host    */
+/* only, for tests): weight_sums k floats, rng a gdd_mt_state advanced as numpy advances it. pairs     */
+/* (2k int64) receives (cluster, batch position) per reassigned centre and *n_pairs their count;        */
+/* weight_sums_out the sums after the fill; *any_zero whether one of them is zero.                      */
+int gdd_minibatch_reassign_host(const float* weight_sums, int k, int64_t batch_size,
+                                float reassignment_ratio, void* rng,
+                                void (*argsort_cb)(const float*, int64_t, int64_t*), int64_t* pairs,
+                                int64_t* n_pairs, float* weight_sums_out, int* any_zero);
 
 /* Host-only numpy-legacy draws used by the native loops (exposed for parity tests):                */
 /* randint(low, high, count) (int64), random_sample(count), permutation(n), and                      */

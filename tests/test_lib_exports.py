@@ -69,6 +69,22 @@ def test_workspace_queries_are_host_only(lib):
     assert lib.gdd_minibatch_step_ws_bytes(1000, 454) >= 8 * 1000 + 4 * 454 + 4 * 1000 + 4
 
 
+def test_minibatch_path_queries_are_host_only(lib):
+    assert lib.gdd_minibatch_step_path(1000, 40, 454, 0) == b"w4/vec/g4xp32"
+    assert lib.gdd_minibatch_fit_path(169343, 40, 454, 1000) in (b"dev/par", b"host")  # host: GDD_HOST_LOOP
+    out = (ctypes.c_int32 * 3)()
+    assert lib.gdd_minibatch_schedule(0, 0, 0, 3, 454, 1000, 0.01, 3, out) == 0 and out[0] & 1
+
+
+def test_an_older_library_is_named_not_crashed_on(monkeypatch):
+    """A libgdd.so built before an entry point existed fails at load with the missing names."""
+    from gdd import _lib
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setitem(_lib.SIGNATURES, "gdd_entry_of_a_later_build", (ctypes.c_int, []))
+    with pytest.raises(RuntimeError, match="older build.*gdd_entry_of_a_later_build"):
+        _lib.load()
+
+
 def test_product_path_refuses_without_device(monkeypatch):
     """No CPU fallback: on a host without a GPU the product raises instead of computing."""
     import torch
