@@ -20,8 +20,8 @@
 // fit one segment write p and update target in the epilogue; split rows write partials that a
 // second kernel folds in order.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 
 #include "gdd_common.hpp"
 
@@ -447,53 +447,70 @@ struct RowMaps {  // relabelled layouts (nullptr: original ids)
   const int32_t* prev;
 };
 
-template <int V, int G>
-void launch_hop_vg(const Plan& pl, const int32_t* col, const float* val, float scale, int d,
-                   const float* x, float* y, float* acc, float acc_scale, const float* acc_init,
-                   const float* acc_prev, RowMaps rm, hipStream_t s) {
-  constexpr int kGroups = 256 / G;
-  const int64_t iblocks = (pl.max_items + kGroups - 1) / kGroups;
-  const int chunks = (d + G * V - 1) / (G * V);
-  auto xcd_launch = [&](auto S_) {
-    constexpr int S = decltype(S_)::value;
-    const int64_t groups = (iblocks + (8 / S) - 1) / (8 / S);
-    k_hop<V, G, S><<<(unsigned)(groups * 8), 256, 0, s>>>(pl.items, pl.counts, col, val, scale, d,
-                                                          x, y, acc, acc_scale, acc_init, acc_prev,
-                                                          pl.partials, rm.y, rm.prev,
-                                                          S == 1 && forced("hop_xcd_contig") ? 1 : 0);
-  };
-  if (chunks == 8)
-    xcd_launch(std::integral_constant<int, 8>());
-  else if (chunks == 4)
-    xcd_launch(std::integral_constant<int, 4>());
-  else if (chunks == 2)
-    xcd_launch(std::integral_constant<int, 2>());
-  else if (chunks == 1)
-    xcd_launch(std::integral_constant<int, 1>());
-  else
-    k_hop<V, G, 0><<<dim3((unsigned)iblocks, (unsigned)chunks), 256, 0, s>>>(
-        pl.items, pl.counts, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, pl.partials,
-        rm.y, rm.prev, 0);
-}
+// ---- the hop's kernel form -----------------------------------------------------------------------
+// k_hop<V, G, S>: V floats per lane, G lanes per item, S XCD feature slices (0: two-dimensional
+// grid). Chosen here only, from d and the buffers' common alignment in bytes (16, 8 or 4); the
+// launchers below switch on the result and gdd_hop_path names it. V == 0: no form (bad arguments).
+struct HopForm {
+  int V, G, S;
+};
 
-// lanes per item: the whole row up to 64 lanes, or narrower groups that split the row into XCD slices
-
-template <int V>
-void launch_hop_v(const Plan& pl, const int32_t* col, const float* val, float scale, int d,
-                  const float* x, float* y, float* acc, float acc_scale, const float* acc_init,
-                  const float* acc_prev, RowMaps rm, hipStream_t s) {
+HopForm hop_form(int d, int align) {
+  if (d <= 0 || (align != 16 && align != 8 && align != 4)) return HopForm{0, 0, 0};
+  // float4 rows need 16-byte aligned row starts: d % 4 == 0 and 16-byte aligned bases
+  const int V = (d % 4 == 0 && align == 16) ? 4 : (d % 2 == 0 && align >= 8) ? 2 : 1;
+  // lanes per item: the whole row up to 64 lanes, or narrower groups that split the row into XCD slices
   const int lanes = (d + V - 1) / V;
   // 29..32 lanes of float4 (d in (112, 128]): two XCD slices of 16 lanes each, so an XCD's L2 caches
   // half of every gathered row (measured at the arxiv shape, d = 128: 202 vs 208 us per hop; the
   // gathers' L2 hit rate rises, the instruction overhead of the narrower groups stays small). With
   // fewer lanes the second slice idles most of its lanes while reading the whole column/value stream
   // again: products' d = 100 (25 lanes) runs 9.5 ms per hop in one 32-lane group vs 12.4 sliced.
-  if (lanes <= 16 || (V == 4 && lanes > 28 && lanes <= 32))
-    launch_hop_vg<V, 16>(pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
-  else if (lanes <= 32)
-    launch_hop_vg<V, 32>(pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
-  else
-    launch_hop_vg<V, 64>(pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
+  const int G = (lanes <= 16 || (V == 4 && lanes > 28 && lanes <= 32)) ? 16 : lanes <= 32 ? 32 : 64;
+  // feature chunks of G*V: 8, 4, 2 or 1 of them map onto the XCDs, any other count walks grid.y
+  const int chunks = (d + G * V - 1) / (G * V);
+  const int S = (chunks == 8 || chunks == 4 || chunks == 2 || chunks == 1) ? chunks : 0;
+  return HopForm{V, G, S};
+}
+
+template <int V, int G, int S>
+void launch_hop(const Plan& pl, const int32_t* col, const float* val, float scale, int d,
+                const float* x, float* y, float* acc, float acc_scale, const float* acc_init,
+                const float* acc_prev, RowMaps rm, hipStream_t s) {
+  constexpr int kGroups = 256 / G;
+  const int64_t iblocks = (pl.max_items + kGroups - 1) / kGroups;
+  if constexpr (S > 0) {
+    const int64_t groups = (iblocks + (8 / S) - 1) / (8 / S);
+    k_hop<V, G, S><<<(unsigned)(groups * 8), 256, 0, s>>>(pl.items, pl.counts, col, val, scale, d,
+                                                          x, y, acc, acc_scale, acc_init, acc_prev,
+                                                          pl.partials, rm.y, rm.prev,
+                                                          S == 1 && forced("hop_xcd_contig") ? 1 : 0);
+  } else {
+    const int chunks = (d + G * V - 1) / (G * V);
+    k_hop<V, G, 0><<<dim3((unsigned)iblocks, (unsigned)chunks), 256, 0, s>>>(
+        pl.items, pl.counts, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, pl.partials,
+        rm.y, rm.prev, 0);
+  }
+}
+
+template <int V, int G, class... A>
+void launch_hop_vg(int S, const A&... a) {
+  switch (S) {
+    case 8: return launch_hop<V, G, 8>(a...);
+    case 4: return launch_hop<V, G, 4>(a...);
+    case 2: return launch_hop<V, G, 2>(a...);
+    case 1: return launch_hop<V, G, 1>(a...);
+    default: return launch_hop<V, G, 0>(a...);
+  }
+}
+
+template <int V, class... A>
+void launch_hop_v(HopForm f, const A&... a) {
+  switch (f.G) {
+    case 16: return launch_hop_vg<V, 16>(f.S, a...);
+    case 32: return launch_hop_vg<V, 32>(f.S, a...);
+    default: return launch_hop_vg<V, 64>(f.S, a...);
+  }
 }
 
 // acc_init (nullable): the accumulator's previous value is acc_scale * acc_init instead of acc (the
@@ -504,19 +521,25 @@ int run_hop(const Plan& pl, const int32_t* rowptr, const int32_t* col, const flo
             float scale, int d, const float* x, float* y, float* acc, float acc_scale,
             hipStream_t s, const float* acc_init = nullptr, const float* acc_prev = nullptr,
             RowMaps rm = RowMaps{nullptr, nullptr}) {
-  // float4 rows need 16-byte aligned row starts: d % 4 == 0 and 16-byte aligned bases
+  // the buffers' common alignment (the partials are written with the rows' vector width too)
   auto aligned = [](const void* p, int a) { return ((uintptr_t)p % a) == 0; };
   const bool a16 = aligned(x, 16) && aligned(y, 16) && (!acc || aligned(acc, 16)) &&
                    (!acc_init || aligned(acc_init, 16)) && (!acc_prev || aligned(acc_prev, 16)) &&
                    aligned(pl.partials, 16);
   const bool a8 = aligned(x, 8) && aligned(y, 8) && (!acc || aligned(acc, 8)) &&
                   (!acc_init || aligned(acc_init, 8)) && (!acc_prev || aligned(acc_prev, 8));
-  if (d % 4 == 0 && a16)
-    launch_hop_v<4>(pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
-  else if (d % 2 == 0 && a8)
-    launch_hop_v<2>(pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
-  else
-    launch_hop_v<1>(pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
+  const HopForm f = hop_form(d, a16 ? 16 : a8 ? 8 : 4);
+  switch (f.V) {
+    case 4:
+      launch_hop_v<4>(f, pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
+      break;
+    case 2:
+      launch_hop_v<2>(f, pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
+      break;
+    default:
+      launch_hop_v<1>(f, pl, col, val, scale, d, x, y, acc, acc_scale, acc_init, acc_prev, rm, s);
+      break;
+  }
   GDD_LAUNCHED();
   const unsigned fixup_grid = (unsigned)std::min<int64_t>(pl.max_long, kFixupBlocks);
   k_fixup<<<fixup_grid, 256, 0, s>>>(pl.counts, pl.long_rows, pl.long_off, rowptr, d, pl.partials, y,
@@ -538,6 +561,14 @@ int check_csr_args(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t*
 }  // namespace gdd
 
 using namespace gdd;
+
+extern "C" const char* gdd_hop_path(int d, int align) {
+  static thread_local char name[32];
+  const HopForm f = hop_form(d, align);
+  if (f.V == 0) return "invalid";
+  snprintf(name, sizeof name, "v%d/g%d/s%d", f.V, f.G, f.S);
+  return name;
+}
 
 extern "C" size_t gdd_propagate_ws_bytes(int64_t n, int64_t nnz, int d) {
   return plan_ws_bytes(n, nnz, d);

@@ -127,6 +127,13 @@ int gdd_spmm_plan(int64_t n, int64_t nnz, const int32_t* rowptr, int d, void* ws
 int gdd_spmm_planned(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* col,
                      const float* val, int d, float scale, const float* x, float* y, float* acc,
                      float acc_scale, const void* ws, size_t ws_bytes, gdd_stream_t stream);
+/* The hop kernel's form for feature width d and the common alignment of a hop's buffers in bytes    */
+/* (16, 8 or 4; x, y, acc and the propagation's internal rows), host only: "v<V>/g<G>/s<S>" with V   */
+/* floats per lane (4, 2, 1), G lanes per work item (16, 32, 64) and S feature slices mapped onto the */
+/* XCDs (8, 4, 2, 1; 0 = a two-dimensional grid over items and feature chunks). Every form computes   */
+/* the same bits. "invalid" for d <= 0 or another align. The string is the calling thread's until its */
+/* next call.                                                                                         */
+const char* gdd_hop_path(int d, int align);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* (a5/a6/a8) k-means building blocks (scikit-learn 1.7.2 semantics, fp32 data)                      */
