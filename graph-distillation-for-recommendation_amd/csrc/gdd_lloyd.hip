@@ -885,6 +885,11 @@ struct LloydState {
   int32_t pad[11];
 };
 static_assert(sizeof(LloydState) == 64, "LloydState is 64 bytes");
+static_assert(offsetof(LloydState, stop_at) == 0, "gdd.h documents stop_at at offset 0");
+static_assert(offsetof(LloydState, reason) == 4, "gdd.h documents reason at offset 4");
+static_assert(offsetof(LloydState, iter) == 8, "gdd.h documents iter at offset 8");
+static_assert(offsetof(LloydState, changed) == 12, "gdd.h documents changed at offset 12");
+static_assert(offsetof(LloydState, done) == 16, "gdd.h documents done at offset 16");
 
 // ---------------------------------------------------------------------------------------------
 // _average_centers + _center_shift

@@ -273,6 +273,17 @@ class MTState(ctypes.Structure):
         rs.set_state(("MT19937", key, int(self.pos), int(self.has_gauss), float(self.gauss)))
 
 
+class LloydState(ctypes.Structure):
+    """gdd_lloyd.hip's LloydState, the Lloyd loop's control words (include/gdd.h states the layout
+    and each word's meaning, gdd_lloyd_state_bytes() the size)."""
+
+    _fields_ = [(w, ctypes.c_int32) for w in ("stop_at", "reason", "iter", "changed", "done")] \
+        + [("pad", ctypes.c_int32 * 11)]
+
+    def driver_words(self):  # what the host's chunk driver decides on
+        return self.stop_at, self.reason, self.iter, self.done
+
+
 ARGSORT_CB = ctypes.CFUNCTYPE(None, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
                               ctypes.POINTER(ctypes.c_int64))
 

@@ -47,6 +47,33 @@ def _as_device_f32(X, device):
     return torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(device)
 
 
+def n_init_of(n_init) -> int:
+    """k-means++ with n_init='auto' is one init (sklearn >= 1.4, _kmeans.py:879-889)."""
+    return 1 if n_init == "auto" else int(n_init)
+
+
+def better_init(inertia, labels, best, k) -> bool:
+    """The best-of-n_init rule (_kmeans.py:1512-1521) against ``best = (labels, inertia, ...)``: the
+    first init, or a lower inertia on a different clustering."""
+    return best is None or (inertia < best[1] and not _same_clustering(labels, best[0], k))
+
+
+def center_columns(X, with_ws: bool):
+    """sklearn's centring on the device (numpy's sequential column sums): X - mean, and the mean and
+    variance of the INPUT's columns (_kmeans.py:1476-1487, :279-288) -> three fp32 device tensors.
+    ``with_ws`` picks the library entry: gdd_center_columns_ws or gdd_center_columns."""
+    n, dim = X.shape
+    lib, stream = _lib.device_lib(), _lib.stream_ptr(X.device)
+    Xc, mean, var = torch.empty_like(X), X.new_empty(dim), X.new_empty(dim)
+    args = (n, dim, X.data_ptr(), Xc.data_ptr(), mean.data_ptr(), var.data_ptr())
+    if with_ws:  # ws is freed on return with the kernel still queued: safe on torch's CURRENT stream only
+        ws = _lib.workspace(lib.gdd_center_columns_ws_bytes(n, dim), X.device)
+        _lib.check(lib.gdd_center_columns_ws(*args, ws.data_ptr(), ws.numel(), stream))
+    else:
+        _lib.check(lib.gdd_center_columns(*args, stream))
+    return Xc, mean, var
+
+
 class _Ops:
     """Device primitives with their workspaces (one instance per fit)."""
 
@@ -179,11 +206,6 @@ class _BaseKMeans:
         self.random_state = random_state
         self.device = device
 
-    def _n_init(self, default):
-        if self.n_init == "auto":
-            return 1  # k-means++ with 'auto' (sklearn >= 1.4, _kmeans.py:879-889)
-        return int(self.n_init)
-
     def fit_predict(self, X, y=None, sample_weight=None):
         return self.fit(X, sample_weight=sample_weight).labels_
 
@@ -292,7 +314,7 @@ class MiniBatchKMeans(_BaseKMeans):
         # loop stops and leaves the per-sample distances in `sq`; their inertia (the sequential
         # fp32 sum, evaluated in parallel by gdd_inertia_ws) runs on a side stream, read on first
         # access of inertia_
-        from .sharded import world_of
+        from .sharded import sharded_labels, world_of
         # only an explicit group shards: with group=None a process in some other job's default
         # group (e.g. a DDP run clustering per rank) fits on its own data
         sharded = self.compute_labels and self.group is not None and world_of(self.group)[1] > 1
@@ -303,7 +325,7 @@ class MiniBatchKMeans(_BaseKMeans):
             sq = torch.empty(n, dtype=torch.float32, device=dev)
         _lib.check(lib.gdd_minibatch_kmeans_fit(
             n, dim, Xd.data_ptr(), k, bs, int(self.max_iter), max_ni, float(self.reassignment_ratio),
-            isz, self._n_init(3), 2 if native_labels else 0, ctypes.addressof(st),
+            isz, n_init_of(self.n_init), 2 if native_labels else 0, ctypes.addressof(st),
             ctypes.cast(_lib.argsort_callback, ctypes.c_void_p).value, centers.data_ptr(),
             labels.data_ptr() if labels is not None else None, sq.data_ptr() if sq is not None else None,
             ctypes.addressof(n_steps), None if native_labels else ctypes.addressof(ewa),
@@ -313,7 +335,6 @@ class MiniBatchKMeans(_BaseKMeans):
         self.n_iter_ = int(np.ceil((self.n_steps_ * bs) / n))
         self.cluster_centers_device_ = centers
         if sharded:  # the final labels pass (:2191-2197) with the rows partitioned over the ranks
-            from .sharded import sharded_labels
             labels, sq, _ = sharded_labels(Xd, centers, group=self.group, with_inertia=True,
                                            fold_inertia=False)
         if self.compute_labels:
@@ -330,7 +351,7 @@ class MiniBatchKMeans(_BaseKMeans):
         n, dim = Xd.shape
         k = self.n_clusters
         bs, isz = self._sizes(n)
-        n_init = self._n_init(3)
+        n_init = n_init_of(self.n_init)
         ops = _Ops(dev, max(n, isz, bs), k, dim)
         validation_indices = rs.randint(0, n, isz)
         best_inertia, init_centers = None, None
@@ -462,16 +483,8 @@ class KMeans(_BaseKMeans):
         dev = X0.device
         import time
         tph = time.perf_counter() if PHASE_TIMING is not None else 0.0
-        # sklearn's centring and _tolerance on the device (numpy's sequential column sums): X - mean,
-        # mean and var of the INPUT (sklearn/cluster/_kmeans.py:1476-1487, :279-288)
-        Xd = torch.empty_like(X0)
-        mean_d = torch.empty(dim, dtype=torch.float32, device=dev)
-        var_d = torch.empty(dim, dtype=torch.float32, device=dev)
-        clib = _lib.device_lib()
-        cws = _lib.workspace(clib.gdd_center_columns_ws_bytes(n, dim), dev)
-        _lib.check(clib.gdd_center_columns_ws(n, dim, X0.data_ptr(), Xd.data_ptr(), mean_d.data_ptr(),
-                                              var_d.data_ptr(), cws.data_ptr(), cws.numel(),
-                                              _lib.stream_ptr(dev)))
+        # sklearn's centring and _tolerance on the device
+        Xd, mean_d, var_d = center_columns(X0, with_ws=True)
         X_mean = mean_d.cpu().numpy()
         tol_ = 0 if self.tol == 0 else np.mean(var_d.cpu().numpy()) * self.tol
         del X0
@@ -490,7 +503,7 @@ class KMeans(_BaseKMeans):
         done, reason = ctypes.c_int32(0), ctypes.c_int32(0)
 
         best = None
-        n_inits = self._n_init(10)
+        n_inits = n_init_of(self.n_init)
         for _ in range(n_inits):
             C0, _ = ops.kmeans_plusplus(Xd, k, rs)
             tph = _phase("kmeans_plusplus", tph)
@@ -536,15 +549,12 @@ class KMeans(_BaseKMeans):
                 return self
             inertia = float(ops.inertia(sq).item())
             lab_h = labels.cpu().numpy()
-            if best is None or (inertia < best[1] and not _same_clustering(lab_h, best[0], k)):
+            if better_init(inertia, lab_h, best, k):
                 best = (lab_h, inertia, C.clone(), n_iter)
-        lab_h, inertia, C, n_iter = best
-        self.labels_ = lab_h
-        self.inertia_ = inertia
+        self.labels_, self.inertia_, C, self.n_iter_ = best
         self.cluster_centers_ = C.cpu().numpy() + X_mean
         self.cluster_centers_device_ = torch.from_numpy(self.cluster_centers_).to(dev)
-        self.labels_device_ = torch.from_numpy(lab_h).to(dev)
-        self.n_iter_ = n_iter
+        self.labels_device_ = torch.from_numpy(self.labels_).to(dev)
         return self
 
     @staticmethod

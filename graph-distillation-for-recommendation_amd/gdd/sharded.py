@@ -30,12 +30,17 @@ tests substitute a CPU stand-in with the same methods to run the distributed log
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
+import os
+import time
+
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _lib
-from .kmeans import KMeans, _Ops, _same_clustering, check_random_state
+from .kmeans import KMeans, _BaseKMeans, _Ops, better_init, center_columns, check_random_state, n_init_of
 
 
 # ------------------------------------------------------------------------------------------------
@@ -61,6 +66,25 @@ def shard_rows(n: int, rank: int, world: int):
     return a, b
 
 
+def _staged(device: torch.device, group) -> bool:
+    """The one place that names a backend: does a tensor on `device` cross `group` through a host
+    copy? A device tensor does unless the backend is RCCL; a host tensor never does."""
+    return device.type == "cuda" and dist.get_backend(group) != "nccl"
+
+
+@contextlib.contextmanager
+def _on_wire(t: torch.Tensor, group, load: bool = True, store: bool = True):
+    """The transport: yields the tensor a collective over `group` runs on in `t`'s place — `t` itself
+    (RCCL: stream-ordered, no host sync, no copy) or, where :func:`_staged` says so, a host copy —
+    empty with ``load=False`` (a pure output) — which is copied back into `t` on exit unless
+    ``store=False`` (a pure input)."""
+    staged = _staged(t.device, group)
+    wire = t if not staged else t.cpu() if load else torch.empty(t.shape, dtype=t.dtype)
+    yield wire
+    if staged and store:
+        t.copy_(wire)
+
+
 def all_gather_parts(t: torch.Tensor, m: int, n: int, group=None, out: torch.Tensor = None) -> torch.Tensor:
     """Concatenate every rank's slice (rank r's first dim holds at most m rows) into the first n rows
     of the whole, in rank order. ``out`` (optional, world * m rows, not aliasing ``t``) receives the
@@ -73,19 +97,11 @@ def all_gather_parts(t: torch.Tensor, m: int, n: int, group=None, out: torch.Ten
     else:
         pad = torch.zeros((m,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
         pad[:t.shape[0]] = t
-    if t.is_cuda and dist.get_backend(group) == "nccl":
-        if out is None:
-            out = torch.empty((world * m,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-        dist.all_gather_into_tensor(out, pad, group=group)
-        return out[:n]
-    host = pad.cpu()
-    parts = [torch.empty_like(host) for _ in range(world)]
-    dist.all_gather(parts, host, group=group)
-    whole = torch.cat(parts, 0)
-    if out is not None:
-        out.copy_(whole)
-        return out[:n]
-    return whole[:n].to(t.device)
+    if out is None:
+        out = torch.empty((world * m,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    with _on_wire(pad, group, store=False) as src, _on_wire(out, group, load=False) as dst:
+        dist.all_gather_into_tensor(dst, src, group=group)
+    return out[:n]
 
 
 def assemble_cols(parts: torch.Tensor, k: int, dim: int, fw: int, world: int) -> torch.Tensor:
@@ -101,81 +117,63 @@ def assemble_cols(parts: torch.Tensor, k: int, dim: int, fw: int, world: int) ->
 
 def all_gather_slots(buf: torch.Tensor, m: int, group=None) -> None:
     """In place: buf holds world * m rows (elements) and rank r's own slot is buf[r*m:(r+1)*m]; every
-    rank ends with every slot. RCCL for device tensors (stream-ordered, no host sync); gloo host-stages."""
+    rank ends with every slot."""
     rank, world = world_of(group)
     if world == 1:
         return
-    mine = buf[rank * m:(rank + 1) * m]
-    if buf.is_cuda and dist.get_backend(group) == "nccl":
-        # a copy of the own slot as the input (ADVICE r4): the in-place form (input a view into the
-        # output) is NCCL-legal but untested on hardware here; the copy is m elements
-        dist.all_gather_into_tensor(buf, mine.clone(), group=group)
-        return
-    host = mine.cpu()
-    parts = [torch.empty_like(host) for _ in range(world)]
-    dist.all_gather(parts, host, group=group)
-    buf.copy_(torch.cat(parts, 0).to(buf.device))
+    # a copy of the own slot as the input (ADVICE r4): the in-place form (input a view into the
+    # output) is NCCL-legal but untested on hardware here; the copy is m elements
+    mine = buf[rank * m:(rank + 1) * m].clone()
+    with _on_wire(mine, group, store=False) as src, _on_wire(buf, group, load=False) as dst:
+        dist.all_gather_into_tensor(dst, src, group=group)
 
 
 def all_reduce_sum(buf: torch.Tensor, group=None) -> None:
-    """In place: every rank's `buf` ends with the element-wise sum over the ranks. RCCL for device
-    tensors (stream-ordered, no host sync); gloo stages through the host. For integer tensors the
-    result does not depend on the collective's algorithm (integer adds are associative)."""
+    """In place: every rank's `buf` ends with the element-wise sum over the ranks. For integer tensors
+    the result does not depend on the collective's algorithm (integer adds are associative)."""
     rank, world = world_of(group)
     if world == 1:
         return
-    if buf.is_cuda and dist.get_backend(group) == "nccl":
-        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
-        return
-    host = buf.cpu() if buf.is_cuda else buf
-    dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
-    if host is not buf:
-        buf.copy_(host)
-
-
-def global_rank(group, r: int) -> int:
-    """The default-group rank of `group`'s rank r (collectives name their source by global rank)."""
-    if group is None or group is dist.group.WORLD:
-        return r
-    return dist.get_global_rank(group, r)
+    with _on_wire(buf, group) as wire:
+        dist.all_reduce(wire, op=dist.ReduceOp.SUM, group=group)
 
 
 _SUBGROUPS = {}
 
 
+def _is_world(group) -> bool:
+    return group is None or group is dist.group.WORLD
+
+
 def subgroup(ranks, group=None):
-    """A process group over `ranks` (ranks of `group`), created once per (group, ranks). Every rank
-    of `group` must call this with the same arguments, members or not (dist.new_group's rule)."""
-    key = (None if group is None or group is dist.group.WORLD else id(group), tuple(ranks))
+    """A process group over the global `ranks`, created once per tuple of ranks. Every process of the
+    default group must call this with the same ranks, members or not (dist.new_group's rule), so only
+    the default group can be split: any other `group` raises, its outsiders would never join in."""
+    if not _is_world(group):
+        raise ValueError("subgroup() splits the default process group only: dist.new_group needs "
+                         "every process of the job, and those outside `group` would not call it")
+    key = tuple(int(r) for r in ranks)
     if key not in _SUBGROUPS:
-        _SUBGROUPS[key] = dist.new_group([global_rank(group, r) for r in ranks])
+        _SUBGROUPS[key] = dist.new_group(list(key))
     return _SUBGROUPS[key]
 
 
 def broadcast_from(tensors, owner: int, group=None) -> None:
     """In place: every rank's `tensors` (contiguous, same shapes on every rank) end with the values
-    that `group`'s rank `owner` holds. RCCL for device tensors (stream-ordered, no host sync); gloo
-    stages through the host."""
+    that `group`'s rank `owner` holds."""
     rank, world = world_of(group)
     if world == 1:
         return
-    src = global_rank(group, owner)
-    nccl = dist.get_backend(group) == "nccl"
+    src = owner if _is_world(group) else dist.get_global_rank(group, owner)  # sources go by global rank
     for t in tensors:
-        if t.is_cuda and nccl:
-            dist.broadcast(t, src=src, group=group)
-            continue
-        h = t.cpu() if t.is_cuda else t
-        dist.broadcast(h, src=src, group=group)
-        if h is not t:
-            t.copy_(h)
+        with _on_wire(t, group) as wire:
+            dist.broadcast(wire, src=src, group=group)
 
 
 def comm_device(group, device):
     """Where a tensor that crosses `group` lives: the GPU under RCCL, the host under gloo."""
-    if world_of(group)[1] > 1 and dist.get_backend(group) != "nccl":
-        return torch.device("cpu")
-    return torch.device(device)
+    device = torch.device(device)
+    return torch.device("cpu") if world_of(group)[1] > 1 and _staged(device, group) else device
 
 
 # ------------------------------------------------------------------------------------------------
@@ -229,12 +227,12 @@ def role_owners(world: int):
 def propagate_roles(adjs, feats, T: int, alpha: float, group=None, ops=None, phases=None):
     """The three propagations of the inductive agent over the ranks: each role graph is normalised
     and propagated by its owners (:func:`role_owners`); train is row-partitioned over its owners
-    (:func:`sharded_propagate` on a sub-group) where :func:`propagation_shards_pay` says so; then one
+    (:func:`sharded_propagate` on a sub-group of the default group) where
+    :func:`propagation_shards_pay` says so; then one
     broadcast per role's target. Every target is the single-GPU loop's, bit for bit. ``adjs`` and
     ``feats`` map role -> graph / N_role x d features (val/test read only on their owners).
     Returns (normalised train graph — computed on every rank, the agent keeps it — and a dict role ->
     target on every rank). ``phases`` (optional dict): synchronised wall ms per stage of this rank."""
-    import time
     ops = ops or DeviceOps(feats["train"].device)
     rank, world = world_of(group)
     owners = role_owners(world)
@@ -256,7 +254,9 @@ def propagate_roles(adjs, feats, T: int, alpha: float, group=None, ops=None, pha
     targets = {}
     tr = owners["train"]
     X = feats["train"]
-    if len(tr) > 1 and propagation_shards_pay(norm_train.n, norm_train.nnz, X.shape[1], len(tr)):
+    # only the default group can make the row split's sub-group; elsewhere train's first owner does it all
+    if (len(tr) > 1 and _is_world(group)
+            and propagation_shards_pay(norm_train.n, norm_train.nnz, X.shape[1], len(tr))):
         sub = subgroup(tr, group)  # every rank creates it; only the members use it
         if rank in tr:
             targets["train"] = sharded_propagate(norm_train, X, T, alpha, group=sub, ops=ops)[0]
@@ -319,12 +319,7 @@ class DeviceOps:
         return propagate(adj_norm, X.to(device=self.device, dtype=torch.float32).contiguous(), T, alpha)
 
     def center(self, X):
-        n, dim = X.shape
-        Xc = torch.empty_like(X)
-        mean = torch.empty(dim, dtype=torch.float32, device=self.device)
-        var = torch.empty(dim, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.gdd_center_columns(n, dim, X.data_ptr(), Xc.data_ptr(), mean.data_ptr(),
-                                               var.data_ptr(), self.stream))
+        Xc, mean, var = center_columns(X, with_ws=False)
         return Xc, mean.cpu().numpy(), var.cpu().numpy()
 
     def kmeans_plusplus(self, X, k, rs):
@@ -343,26 +338,8 @@ class DeviceOps:
         from .cluster import group_by_label
         return group_by_label(labels, k)
 
-    def mstep(self, X, grp, k, c0, c1):
-        n, dim = X.shape
-        perm, offsets = grp
-        sums = torch.empty((c1 - c0, dim), dtype=torch.float32, device=self.device)
-        wsum = torch.empty(c1 - c0, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.gdd_segment_sum_f32_part(n, dim, X.data_ptr(), None, perm.data_ptr(),
-                                                     offsets.data_ptr(), k, c0, c1, _lib.ptr(sums),
-                                                     _lib.ptr(wsum), self.stream))
-        return sums, wsum
-
     def relocate(self, X, C_old, sums, wsum, labels):
         KMeans._relocate(X, C_old, sums, wsum, labels, _Ops(self.device, 1, C_old.shape[0], X.shape[1]))
-
-    def average(self, sums, wsum, C_old):
-        k, dim = sums.shape
-        C_new = sums.clone()
-        shift = torch.empty(k, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.gdd_average_centers(k, dim, C_new.data_ptr(), wsum.data_ptr(),
-                                                C_old.data_ptr(), shift.data_ptr(), self.stream))
-        return C_new, shift
 
     def point_sqdist(self, X, labels, C, r0, r1):
         out = torch.empty(r1 - r0, dtype=torch.float32, device=self.device)
@@ -394,9 +371,10 @@ class DeviceOps:
             parts=torch.zeros(world * k * fw, dtype=torch.float32, device=dev))
 
     def lloyd_clear(self, ctx, resume):
-        ctx.state[:12].zero_()  # stop_at, reason, iter
+        changed = _lib.LloydState.changed
+        ctx.state[:changed.offset].zero_()  # stop_at, reason, iter
         if not resume:
-            ctx.state[12:16].zero_()  # the labels-changed flag
+            ctx.state[changed.offset:changed.offset + changed.size].zero_()  # the labels-changed flag
             ctx.labels_old.fill_(-1)
 
     def lloyd_estep(self, ctx, X, C, r0, r1, first, it):
@@ -445,8 +423,8 @@ class DeviceOps:
 
     def lloyd_state_begin(self, ctx):
         """Start the state's device-to-host copy (pinned, stream-ordered); lloyd_state_end waits."""
-        h = torch.empty(8, dtype=torch.int32, pin_memory=True)
-        h.copy_(ctx.state[:32].view(torch.int32), non_blocking=True)
+        h = torch.empty(ctypes.sizeof(_lib.LloydState), dtype=torch.uint8, pin_memory=True)
+        h.copy_(ctx.state, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         return h, ev
@@ -455,7 +433,7 @@ class DeviceOps:
         """(stop_at, reason, iter, done) of the copy lloyd_state_begin started."""
         h, ev = handle
         ev.synchronize()
-        return int(h[0]), int(h[1]), int(h[2]), int(h[4])
+        return _lib.LloydState.from_buffer(h.numpy()).driver_words()
 
     def rows_plan(self, rows_graph, d):
         from .graph import SpMMPlan
@@ -482,18 +460,24 @@ HOP_GATHER_GBS = 5500.0  # random whole-row gathers from HBM (MI355X_MICROARCH.m
 ALLGATHER_GBS = 300.0    # RCCL all-gather bus bandwidth per GPU over xGMI (planning figure), GB/s
 
 
+def _forced(switch: str, world: int):
+    """A size model's answer where it is not the model's to give: GDD_SHARD_*=1/0 forces it (one
+    rank never splits), and without the switch one rank does not split either. None: ask the model."""
+    env = os.environ.get(switch)
+    if env is not None:
+        return env == "1" and world > 1
+    return False if world <= 1 else None
+
+
 def propagation_shards_pay(n: int, nnz: int, d: int, world: int) -> bool:
     """Size model for row-partitioned propagation: a hop's gathers (nnz rows of d fp32, whole 128-B
     lines, at the HBM gather rate) shrink by (R-1)/R; each hop then all-gathers the N x d output
     ((R-1)/R of it crosses xGMI). ogbn-products (130M entries, d=100): ~12 ms of gathers vs ~2.9 ms
     of all-gather at R=8 -> shard; ogbn-arxiv (2.6M, d=128): 0.21 vs 0.25 ms -> replicate.
     GDD_SHARD_PROP=1/0 forces the choice."""
-    import os
-    env = os.environ.get("GDD_SHARD_PROP")
-    if env is not None:
-        return env == "1" and world > 1
-    if world <= 1:
-        return False
+    forced = _forced("GDD_SHARD_PROP", world)
+    if forced is not None:
+        return forced
     line = 128
     row_bytes = -(-4 * d // line) * line
     frac = (world - 1) / world
@@ -594,12 +578,9 @@ def lloyd_rows_pay(n: int, dim: int, k: int, world: int) -> bool:
     unbounded E-step (2 n k dim flops) of 1 ms and more shards. The M-step is not split: its ordered per-cluster folds are bound by the longest member
     chain, not by the rows' bytes (a column split measured 1.53 -> 1.49 / 1.57 / 1.59 ms at 1/2, 1/4,
     1/8 of the columns, `profiles/r04_fold_cols.txt`). GDD_SHARD_LLOYD=1/0 forces the choice."""
-    import os
-    env = os.environ.get("GDD_SHARD_LLOYD")
-    if env is not None:
-        return env == "1" and world > 1
-    if world <= 1:
-        return False
+    forced = _forced("GDD_SHARD_LLOYD", world)
+    if forced is not None:
+        return forced
     bounded = dim <= 48  # the bounded E-step's shapes (gdd_lloyd.hip lloyd_prune_ok)
     # bounded: the bounds test plus the listed rows' exact pass, measured 233 us per iteration at the
     # products shape (2.45M rows, a third of them listed; r06 kernel trace, tools/prof_products_lloyd.py)
@@ -610,23 +591,128 @@ def lloyd_rows_pay(n: int, dim: int, k: int, world: int) -> bool:
     return estep_ms * frac > gather_ms
 
 
-class ShardedKMeans:
+def run_chunks(mode, Cb, it0: int, resume: bool, first_e: int, max_iter: int):
+    """Iterations it0.. of one mode's phase loop until the state's stop word is set or max_iter ->
+    (stop_at, reason, iter, done). Iteration i reads C[i % 2] and writes C[(i+1) % 2]; with `resume`
+    iteration it0 is only the mode's update from the relocated sums. The host reads the state once per
+    chunk (2, 4, then 8 iterations), one chunk behind — chunk c's copy is waited for after chunk c+1
+    is enqueued — as gdd_kmeans_lloyd_run does. The M-step and update kernels are gated by the stop
+    word, so iterations enqueued past a stop change nothing. Needs no process group and no device."""
+    ops, ctx = mode.ops, mode.ctx
+    start, ch, pending = it0, 2, None
+    while start < max_iter:
+        stop = min(start + ch, max_iter)
+        for i in range(start, stop):
+            if resume and i == it0:  # C[(i+1) % 2] already holds the relocated sums
+                mode.update(Cb[i % 2], Cb[(i + 1) % 2], i, True)
+            else:
+                mode.iteration(Cb[i % 2], Cb[(i + 1) % 2], i, i == first_e)
+        handle = ops.lloyd_state_begin(ctx)
+        if pending is not None:
+            st = ops.lloyd_state_end(pending)  # the previous chunk's decision, read while this one runs
+            if st[0]:
+                return st
+        start, ch, pending = stop, min(ch * 2, 8), handle
+    if pending is not None:
+        st = ops.lloyd_state_end(pending)
+        if st[0]:
+            return st
+    return 0, 0, 0, max_iter  # ran out of iterations (sklearn's loop end)
+
+
+class _Rows:
+    """The phase loop's default mode: after the E-step on this rank's rows, ONE all-gather of the
+    labels, the replicated ordered M-step over all columns (into the next centres' buffer), update."""
+
+    name, split = "rows", False
+
+    def __init__(self, ops, Xc, k, rank, world, group, tol):
+        self.ops, self.X, self.group, self.tol, self.rank, self.world = ops, Xc, group, tol, rank, world
+        n, dim = Xc.shape
+        self.r0, self.r1, self.m = part(n, rank, world)  # this rank's rows, and its M-step columns
+        self.f0, self.f1, self.fw = part(dim, rank, world) if self.split else (0, dim, dim)
+        self.ctx = ops.lloyd_begin(n, dim, k, world, self.m, self.fw if self.split else 1)
+        self.labels = self.ctx.labels[:n]
+        self.mine = self.ctx.parts[rank * k * self.fw:][:k * self.fw].view(k, self.fw) if self.split else None
+
+    def iteration(self, C_old, C_new, i, first):
+        self.ops.lloyd_estep(self.ctx, self.X, C_old, self.r0, self.r1, first, i)
+        self.sums(C_new, i)
+        self.update(C_old, C_new, i, False)
+
+    def sums(self, C_new, i):
+        all_gather_slots(self.ctx.labels, self.m, self.group)
+        self.ops.lloyd_mstep(self.ctx, self.X, 0, self.ctx.dim, C_new, i)
+
+    def update(self, C_old, C_new, i, resumed):  # resumed: C_new already holds the relocated sums
+        self.ops.lloyd_update(self.ctx, None, self.fw, C_new, C_old, self.tol, i)
+
+    def gather_labels(self):
+        """Every row's label on every rank (for a relocation, or as a strict stop's result): as it is."""
+
+    def gather_sums(self, C_new):
+        """The k x dim sums in C_new (for a relocation): the M-step wrote them there."""
+
+
+class _RowsCols(_Rows):
+    """``split_columns``: the M-step folds this rank's feature columns only; ONE more all-gather, of
+    the k x fw column slices, and the update assembles the sums from them."""
+
+    split = True
+
+    def sums(self, C_new, i):
+        ctx, k, fw = self.ctx, self.ctx.k, self.fw
+        all_gather_slots(ctx.labels, self.m, self.group)
+        self.ops.lloyd_mstep(ctx, self.X, self.f0, self.f1, self.mine, i)
+        all_gather_slots(ctx.parts, k * fw, self.group)
+
+    def update(self, C_old, C_new, i, resumed):
+        parts = None if resumed else self.ctx.parts
+        self.ops.lloyd_update(self.ctx, parts, self.fw, C_new, C_old, self.tol, i)
+
+    def gather_sums(self, C_new):  # they are still in the ranks' slices
+        C_new.copy_(assemble_cols(self.ctx.parts, self.ctx.k, self.ctx.dim, self.fw, self.world))
+
+
+class _Reduce(_Rows):
+    """``mstep="reduce"``: each rank sums its own rows as int64 fixed point (``q = rint(x * 2^e_f)``,
+    the exponents fixed once per fit so that no sum can overflow; include/gdd.h), ONE SUM
+    all-reduce of the ``k*(dim+1)+1`` sums / counts / changed count replaces the labels all-gather,
+    and the replicated update rounds the sums to fp32 once. The collective is not gated by the stop
+    word: past a stop the local phase only zeroes the buffer, the all-reduce sums zeros, and nothing
+    reads it — what a resume needs is in C[(i+1) % 2], wsum and the state word. Each rank holds only
+    its own rows' labels until a relocation or a strict stop needs them all: ONE all-gather."""
+
+    name = "reduce"
+
+    def __init__(self, ops, Xc, k, rank, world, group, tol):
+        super().__init__(ops, Xc, k, rank, world, group, tol)
+        ops.lloyd_reduce_begin(self.ctx)
+        ops.lloyd_reduce_exponents(self.ctx, Xc)  # on the device: no host sync
+
+    def sums(self, C_new, i):
+        self.ops.lloyd_reduce_local(self.ctx, self.X, self.r0, self.r1, i)
+        all_reduce_sum(self.ctx.rbuf, self.group)
+
+    def update(self, C_old, C_new, i, resumed):
+        self.ops.lloyd_reduce_update(self.ctx, resumed, C_new, C_old, self.tol, i)
+
+    def gather_labels(self):
+        all_gather_slots(self.ctx.labels, self.m, self.group)
+
+
+class ShardedKMeans(_BaseKMeans):
     """sklearn KMeans(n_clusters, n_init, max_iter, tol, random_state).fit (Lloyd, _kmeans.py:
     1427-1530 / :624-752) over a process group. ``fit`` takes the whole input on every rank; every
     rank ends with the same fitted attributes, bit-identical to one GPU. Where :func:`lloyd_rows_pay`
-    says a row split pays, the device loop runs in phases — the E-step on this rank's rows, an
-    all-gather of the labels, the replicated M-step (or, with ``split_columns``, this rank's feature
-    columns and an all-gather of the column slices) and update; otherwise every rank runs the
+    says a row split pays, the device loop runs in phases, driven by :func:`run_chunks` in one of the
+    modes :class:`_Rows` or (``split_columns``) :class:`_RowsCols`; otherwise every rank runs the
     single-GPU device loop (`gdd.KMeans`) on the replicated input, with no collective at all.
 
-    ``mstep="reduce"`` (opt-in, ``mode_ == "reduce"`` for every world size) splits the M-step too:
-    each rank sums its own rows as int64 fixed point (``q = rint(x * 2^e_f)``, the exponents fixed
-    once per fit so that no sum can overflow; include/gdd.h), ONE SUM all-reduce of
-    ``k*(dim+1)+1`` int64 words per iteration replaces the labels all-gather, and the sums are rounded
-    to fp32 once before the usual averaging and convergence test. Integer sums are exact and
-    associative, so the fit is bit-identical for any number of ranks, any row split and any
-    reduction order — but it is its own arithmetic, not scikit-learn's ordered fp32 chains: labels
-    and ``n_iter_`` agree with scikit-learn on the tested inputs, centres to a few 1e-6 relative."""
+    ``mstep="reduce"`` (opt-in, ``mode_ == "reduce"`` for every world size) is :class:`_Reduce`.
+    Integer sums are exact and associative, so that fit is bit-identical for any number of ranks, row
+    split and reduction order — but it is its own arithmetic, not scikit-learn's ordered fp32 chains:
+    labels and ``n_iter_`` agree with scikit-learn on the tested inputs, centres to a few 1e-6."""
 
     def __init__(self, n_clusters=8, *, n_init="auto", max_iter=300, tol=1e-4, random_state=None,
                  group=None, ops=None, device="cuda", split_columns=False, mstep="ordered"):
@@ -634,174 +720,67 @@ class ShardedKMeans:
             raise ValueError(f"mstep must be 'ordered' or 'reduce', got {mstep!r}")
         if mstep == "reduce" and split_columns:
             raise ValueError("split_columns splits the ordered M-step; mstep='reduce' has no column split")
-        self.mstep = mstep
-        self.n_clusters = n_clusters
-        self.n_init = n_init
-        self.max_iter = max_iter
-        self.tol = tol
-        self.random_state = random_state
-        self.group = group
-        self.ops = ops
-        self.device = device
-        self.split_columns = split_columns
+        super().__init__(n_clusters, n_init=n_init, max_iter=max_iter, tol=tol, random_state=random_state,
+                         device=device)
+        self.mstep, self.split_columns, self.group, self.ops = mstep, split_columns, group, ops
 
     def fit(self, X, y=None, sample_weight=None):
-        if sample_weight is not None and not np.all(np.asarray(sample_weight) == 1):
-            raise NotImplementedError("non-unit sample_weight is not used by the reference")
-        group = self.group
+        self._check_weights(sample_weight)
+        group, k, reduce = self.group, self.n_clusters, self.mstep == "reduce"
         rank, world = world_of(group)
-        n_all, dim_all = X.shape
-        reduce = self.mstep == "reduce"
-        if reduce and self.split_columns:
-            raise ValueError("split_columns splits the ordered M-step; mstep='reduce' has no column split")
-        if not reduce and self.ops is None and not lloyd_rows_pay(n_all, dim_all, self.n_clusters, world):
+        if not reduce and self.ops is None and not lloyd_rows_pay(X.shape[0], X.shape[1], k, world):
             # replicated: the single-GPU device loop on every rank (same RandomState, same bits)
-            km = KMeans(n_clusters=self.n_clusters, n_init=self.n_init, max_iter=self.max_iter,
+            km = KMeans(n_clusters=k, n_init=self.n_init, max_iter=self.max_iter,
                         tol=self.tol, random_state=self.random_state, device=self.device).fit(X)
             for a in ("labels_", "labels_device_", "inertia_", "cluster_centers_",
                       "cluster_centers_device_", "n_iter_"):
                 setattr(self, a, getattr(km, a))
             self.mode_ = "replicated"
             return self
-        self.mode_ = "reduce" if reduce else "rows"
         ops = self.ops or DeviceOps(self.device)
         X = ops.tensor(X, dtype=torch.float32)
-        n, dim = X.shape
-        k = self.n_clusters
+        n = X.shape[0]
         if k > n:
             raise ValueError(f"n_samples={n} should be >= n_clusters={k}.")
-        r0, r1, m = part(n, rank, world)
-        split = self.split_columns and world > 1
-        # this rank's feature columns of the M-step (all of them unless split_columns)
-        f0, f1, fw = part(dim, rank, world) if split else (0, dim, dim)
         rs = check_random_state(self.random_state)
         # centring and _tolerance on the whole (replicated) input, numpy's orders (:1476-1487, :279-288)
         Xc, X_mean, var = ops.center(X)
         tol_ = 0 if self.tol == 0 else np.mean(var) * self.tol
-        n_init = 1 if self.n_init == "auto" else int(self.n_init)
-        ctx = ops.lloyd_begin(n, dim, k, world, m, fw if split else 1)
-        if reduce:
-            ops.lloyd_reduce_begin(ctx)
-            ops.lloyd_reduce_exponents(ctx, Xc)  # on the device: no host sync
-        labels = ctx.labels[:n]
-        mine = ctx.parts[rank * k * fw:(rank + 1) * k * fw].view(k, fw) if split else None
+        mode = (_Reduce if reduce else _RowsCols if self.split_columns and world > 1 else _Rows)(
+            ops, Xc, k, rank, world, group, tol_)
+        self.mode_ = mode.name
+        ctx, r0, r1, m = mode.ctx, mode.r0, mode.r1, mode.m
         best = None
-        for _ in range(n_init):
+        for _ in range(n_init_of(self.n_init)):
             C0 = ops.kmeans_plusplus(Xc, k, rs)  # same RandomState on every rank: same centres
             Cb = (C0.contiguous(), torch.empty_like(C0))
             it0, resume, first_e = 0, False, 0
             while True:  # _kmeans_single_lloyd (:690-735), enqueued in chunks of iterations
                 ops.lloyd_clear(ctx, resume)
-                if reduce:
-                    stop_at, reason, it_r, done = self._run_chunks_reduce(ops, ctx, Xc, Cb, it0, resume,
-                                                                         first_e, (r0, r1, m), tol_, group)
-                else:
-                    stop_at, reason, it_r, done = self._run_chunks(ops, ctx, Xc, Cb, it0, resume, first_e,
-                                                                  (r0, r1, m), (f0, f1, fw, split), mine,
-                                                                  tol_, group)
+                _, reason, it, n_iter = run_chunks(mode, Cb, it0, resume, first_e, self.max_iter)
                 if reason != 3:
                     break
-                if reduce:  # the rare path's one labels all-gather: the relocation reads every row's label
-                    all_gather_slots(ctx.labels, m, group)
-                # an empty cluster at iteration it_r (rare): the sums to C[(it+1) % 2], sklearn's
+                # an empty cluster at iteration it (rare): the sums to C[(it+1) % 2], sklearn's
                 # relocation on the host (replicated, identical on every rank), then resume there
-                it = it_r
                 C_new = Cb[(it + 1) % 2]
-                if split:  # otherwise the M-step wrote the sums there itself
-                    C_new.copy_(assemble_cols(ctx.parts, k, dim, fw, world))
-                ops.relocate(Xc, Cb[it % 2], C_new, ctx.wsum, labels)
+                mode.gather_labels()
+                mode.gather_sums(C_new)
+                ops.relocate(Xc, Cb[it % 2], C_new, ctx.wsum, mode.labels)
                 it0, resume, first_e = it, True, it + 1
-            n_iter = done
-            strict = reason == 1
             C = Cb[n_iter % 2]  # iteration i writes C[(i+1) % 2]
-            if not strict:  # the final E-step with the last centres (:736-747)
-                lab, _ = ops.assign(Xc, C, r0, r1)
-                lab_full = all_gather_parts(lab, m, n, group)
-            else:
-                if reduce:  # each rank holds its own rows' labels: the one all-gather of this init
-                    all_gather_slots(ctx.labels, m, group)
-                lab_full = labels.clone()
+            if reason == 1:  # strict convergence: the loop's labels are the final ones
+                mode.gather_labels()
+                lab_full = mode.labels.clone()
+            else:  # the final E-step with the last centres (:736-747)
+                lab_full = all_gather_parts(ops.assign(Xc, C, r0, r1)[0], m, n, group)
             sq = all_gather_parts(ops.point_sqdist(Xc, lab_full, C, r0, r1), m, n, group)
             inertia = ops.inertia(sq)
             lab_h = lab_full.cpu().numpy()
-            if best is None or (inertia < best[1] and not _same_clustering(lab_h, best[0], k)):
+            if better_init(inertia, lab_h, best, k):
                 best = (lab_h, inertia, C.clone(), n_iter, lab_full.clone())
-        lab_h, inertia, C, n_iter, labels_best = best
-        self.labels_ = lab_h
-        self.labels_device_ = labels_best
-        self.inertia_ = inertia
+        self.labels_, self.inertia_, C, self.n_iter_, self.labels_device_ = best
         self.cluster_centers_ = C.cpu().numpy() + X_mean
         self.cluster_centers_device_ = ops.tensor(self.cluster_centers_, dtype=torch.float32)
-        self.n_iter_ = n_iter
         return self
 
-    def _run_chunks(self, ops, ctx, Xc, Cb, it0, resume, first_e, rows, cols, mine, tol_, group):
-        """Iterations it0.. until the state's stop word is set or max_iter: each iteration is the
-        E-step on this rank's rows, ONE all-gather of the labels, the M-step (all columns, into the
-        next centres' buffer; or this rank's columns and ONE all-gather of the column slices), the
-        replicated update; the host reads the state once per chunk (2, 4, then 8 iterations), one
-        chunk behind, as gdd_kmeans_lloyd_run does. The M-step and update kernels are gated by the
-        stop word, so iterations enqueued past a stop change nothing."""
-        r0, r1, m = rows
-        f0, f1, fw, split = cols
-        i, ch, pending = it0, 2, None
-        while i < self.max_iter:
-            for _ in range(min(ch, self.max_iter - i)):
-                if not (resume and i == it0):
-                    ops.lloyd_estep(ctx, Xc, Cb[i % 2], r0, r1, i == first_e, i)
-                    all_gather_slots(ctx.labels, m, group)
-                    if split:
-                        ops.lloyd_mstep(ctx, Xc, f0, f1, mine, i)
-                        all_gather_slots(ctx.parts, ctx.k * fw, group)
-                        ops.lloyd_update(ctx, ctx.parts, fw, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
-                    else:
-                        ops.lloyd_mstep(ctx, Xc, 0, ctx.dim, Cb[(i + 1) % 2], i)
-                        ops.lloyd_update(ctx, None, ctx.dim, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
-                else:  # resume after a relocation: C[(i+1) % 2] already holds the relocated sums
-                    ops.lloyd_update(ctx, None, fw, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
-                i += 1
-            handle = ops.lloyd_state_begin(ctx)
-            if pending is not None:
-                st = ops.lloyd_state_end(pending)  # the previous chunk's decision, read while this one runs
-                if st[0]:
-                    return st
-            pending = handle
-            ch = min(ch * 2, 8)
-        st = ops.lloyd_state_end(pending) if pending is not None else (0, 0, 0, 0)
-        if st[0]:
-            return st
-        return 0, 0, 0, self.max_iter  # ran out of iterations (sklearn's loop end)
-
-    def _run_chunks_reduce(self, ops, ctx, Xc, Cb, it0, resume, first_e, rows, tol_, group):
-        """:meth:`_run_chunks` for ``mstep="reduce"``: each iteration is the E-step on this rank's rows,
-        the rank's int64 sums / counts / changed count, ONE SUM all-reduce of that buffer, and the
-        replicated update from it. The collective is not gated by the stop word: past a stop the local
-        phase only zeroes the buffer, the all-reduce sums zeros, and nothing reads it — what a resume
-        after a relocation needs is in C[(i+1) % 2], wsum and the state word."""
-        r0, r1, m = rows
-        i, ch, pending = it0, 2, None
-        while i < self.max_iter:
-            for _ in range(min(ch, self.max_iter - i)):
-                if not (resume and i == it0):
-                    ops.lloyd_estep(ctx, Xc, Cb[i % 2], r0, r1, i == first_e, i)
-                    ops.lloyd_reduce_local(ctx, Xc, r0, r1, i)
-                    all_reduce_sum(ctx.rbuf, group)
-                    ops.lloyd_reduce_update(ctx, False, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
-                else:  # resume after a relocation: C[(i+1) % 2] already holds the relocated sums
-                    ops.lloyd_reduce_update(ctx, True, Cb[(i + 1) % 2], Cb[i % 2], tol_, i)
-                i += 1
-            handle = ops.lloyd_state_begin(ctx)
-            if pending is not None:
-                st = ops.lloyd_state_end(pending)  # the previous chunk's decision, read while this one runs
-                if st[0]:
-                    return st
-            pending = handle
-            ch = min(ch * 2, 8)
-        st = ops.lloyd_state_end(pending) if pending is not None else (0, 0, 0, 0)
-        if st[0]:
-            return st
-        return 0, 0, 0, self.max_iter  # ran out of iterations (sklearn's loop end)
-
-    def fit_predict(self, X, y=None, sample_weight=None):
-        return self.fit(X, sample_weight=sample_weight).labels_
 

@@ -374,6 +374,16 @@ int gdd_relocate_distances(int64_t n, int dim, const float* X, const int32_t* la
 /* For dim <= 48 with every centre in one LDS chunk, the E-step is bounded: a row whose Hamerly      */
 /* bounds, widened by the fp32 rounding margin, prove sklearn's argmin keeps its label skips the     */
 /* distance pass (labels identical; the workspace holds the bounds; GDD_LLOYD_PRUNE=0 disables).     */
+/* The state's layout (64 bytes, int32 words; the phase entry points below share it). Iteration i    */
+/* runs as steps 2i (E-step, sums, empty-cluster check) and 2i+1 (average, shift, convergence):      */
+/*   offset  0  stop_at  0 while running, s+1 once step s stopped: every later step's kernels no-op  */
+/*   offset  4  reason   0 running / max_iter, 1 strict, 2 tol, 3 an empty cluster needs relocation  */
+/*   offset  8  iter     the iteration the reason refers to                                          */
+/*   offset 12  changed  labels changed in the current iteration (kept across a relocation's resume) */
+/*   offset 16  done     iterations completed                                                        */
+/*   offset 20  11 words of padding                                                                  */
+/* A caller of the phase entry points zeroes stop_at, reason and iter before each run, and changed   */
+/* too unless it resumes after a relocation (gdd._lib.LloydState mirrors the struct).                */
 size_t gdd_lloyd_state_bytes(void);
 size_t gdd_kmeans_lloyd_ws_bytes(int64_t n, int dim, int k);
 size_t gdd_kmeans_lloyd_host_ws_bytes(void);

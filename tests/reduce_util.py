@@ -58,19 +58,19 @@ class ReduceOps(OracleOps):
             C_new.copy_(torch.from_numpy(sums))
             ctx.wsum.copy_(torch.from_numpy(w))
             if buf[-1] != 0:
-                ctx.state[3] = 1
+                ctx.state.changed = 1
             if np.any(buf[k * dim:k * dim + k] == 0):
-                ctx.state[1], ctx.state[2], ctx.state[0] = 3, it, 2 * it + 1
+                ctx.state.reason, ctx.state.iter, ctx.state.stop_at = 3, it, 2 * it + 1
                 return
         cn, shift = self.average(C_new, ctx.wsum, C_old)
         C_new.copy_(cn)
         ctx.shift.copy_(shift)
         reason = 0
-        if ctx.state[3] == 0:
+        if ctx.state.changed == 0:
             reason = 1
         elif float((shift.numpy() ** 2).sum()) <= tol:  # numpy's pairwise fp32 sum
             reason = 2
-        ctx.state[3] = 0
-        ctx.state[4] = it + 1
+        ctx.state.changed = 0
+        ctx.state.done = it + 1
         if reason:
-            ctx.state[1], ctx.state[2], ctx.state[0] = reason, it, 2 * it + 2
+            ctx.state.reason, ctx.state.iter, ctx.state.stop_at = reason, it, 2 * it + 2

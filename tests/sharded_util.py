@@ -6,6 +6,7 @@ import socket
 import numpy as np
 import torch
 
+from gdd._lib import LloydState
 from oracle import oracle as O
 
 
@@ -41,13 +42,6 @@ class OracleOps:
     def group(self, labels, k):
         return _np(labels).astype(np.int32)
 
-    def mstep(self, X, grp, k, c0, c1):
-        x = np.ascontiguousarray(_np(X), np.float32)
-        sums = np.empty((k, x.shape[1]), np.float32)
-        wic = np.empty(k, np.float32)
-        O.lib().oracle_segment_sum_f32(x.shape[0], x.shape[1], x, None, grp, k, sums, wic)
-        return torch.from_numpy(sums[c0:c1].copy()), torch.from_numpy(wic[c0:c1].copy())
-
     def relocate(self, X, C_old, sums, wsum, labels):
         s, w = sums.numpy(), wsum.numpy()  # views: modified in place
         O._relocate_empty(_np(X), _np(C_old), s, w, _np(labels))
@@ -71,7 +65,7 @@ class OracleOps:
     # -- the Lloyd loop in phases: the oracle's arithmetic with the device's stop-word gating ------
     def lloyd_begin(self, n, dim, k, world, m, fw):
         from types import SimpleNamespace
-        return SimpleNamespace(n=n, dim=dim, k=k, state=np.zeros(16, np.int32),
+        return SimpleNamespace(n=n, dim=dim, k=k, state=LloydState(),
                                labels=torch.zeros(world * m, dtype=torch.int32),
                                labels_old=torch.empty(n, dtype=torch.int32),
                                wsum=torch.empty(k, dtype=torch.float32),
@@ -80,13 +74,13 @@ class OracleOps:
 
     @staticmethod
     def _stopped(ctx, step):
-        v = int(ctx.state[0])
+        v = ctx.state.stop_at
         return v != 0 and v - 1 < step
 
     def lloyd_clear(self, ctx, resume):
-        ctx.state[:3] = 0
+        ctx.state.stop_at = ctx.state.reason = ctx.state.iter = 0
         if not resume:
-            ctx.state[3] = 0
+            ctx.state.changed = 0
             ctx.labels_old.fill_(-1)
 
     def lloyd_estep(self, ctx, X, C, r0, r1, first, it):
@@ -108,7 +102,7 @@ class OracleOps:
             out.view(-1)[:k * (f1 - f0)] = torch.from_numpy(np.ascontiguousarray(sums[:, f0:f1]).ravel())
         ctx.wsum[:] = torch.from_numpy(wic)
         if np.any(wic == 0):  # k_lloyd_check_empty
-            ctx.state[1], ctx.state[2], ctx.state[0] = 3, it, 2 * it + 1
+            ctx.state.reason, ctx.state.iter, ctx.state.stop_at = 3, it, 2 * it + 1
 
     def lloyd_update(self, ctx, parts, fw, C_new, C_old, tol, it):
         if self._stopped(ctx, 2 * it + 1):
@@ -122,23 +116,23 @@ class OracleOps:
         ctx.shift.copy_(shift)
         lab = ctx.labels[:ctx.n]
         if bool((lab != ctx.labels_old).any()):  # k_lloyd_changed
-            ctx.state[3] = 1
+            ctx.state.changed = 1
             ctx.labels_old.copy_(lab)
         reason = 0
-        if ctx.state[3] == 0:
+        if ctx.state.changed == 0:
             reason = 1
         elif float((shift.numpy() ** 2).sum()) <= tol:  # numpy's pairwise fp32 sum
             reason = 2
-        ctx.state[3] = 0
-        ctx.state[4] = it + 1
+        ctx.state.changed = 0
+        ctx.state.done = it + 1
         if reason:
-            ctx.state[1], ctx.state[2], ctx.state[0] = reason, it, 2 * it + 2
+            ctx.state.reason, ctx.state.iter, ctx.state.stop_at = reason, it, 2 * it + 2
 
     def lloyd_state_begin(self, ctx):
-        return ctx.state.copy()
+        return LloydState.from_buffer_copy(ctx.state)
 
     def lloyd_state_end(self, h):
-        return int(h[0]), int(h[1]), int(h[2]), int(h[4])
+        return h.driver_words()
 
     def rows_plan(self, rows_graph, d):
         return (_np(rows_graph.rowptr), _np(rows_graph.col), _np(rows_graph.values()))

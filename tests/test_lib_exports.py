@@ -69,6 +69,11 @@ def test_workspace_queries_are_host_only(lib):
     assert lib.gdd_minibatch_step_ws_bytes(1000, 454) >= 8 * 1000 + 4 * 454 + 4 * 1000 + 4
 
 
+def test_lloyd_state_struct_has_the_library_size(lib):
+    from gdd import _lib
+    assert lib.gdd_lloyd_state_bytes() == ctypes.sizeof(_lib.LloydState) == 64
+
+
 def test_minibatch_path_queries_are_host_only(lib):
     assert lib.gdd_minibatch_step_path(1000, 40, 454, 0) == b"w4/vec/g4xp32"
     assert lib.gdd_minibatch_fit_path(169343, 40, 454, 1000) in (b"dev/par", b"host")  # host: GDD_HOST_LOOP
