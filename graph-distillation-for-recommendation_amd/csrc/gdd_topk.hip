@@ -17,6 +17,11 @@
 // order. The score of (user, item) is one fmaf chain over f = 0 .. d-1 from +0: float4 LDS reads of
 // the item row feed the chain in ascending f, the d % 4 tail is read one by one.
 //
+// gdd_cluster_expand_topk: the same lists for a condensed model (every user of a cluster shares a
+// row, every item of a cluster a score) from gdd_score_topk's ranking of the item clusters per user
+// cluster: one wave per user expands that ranking into item ids with the same append / select /
+// threshold scheme (k_cluster_expand_topk below).
+//
 // gdd_rank_metrics: one wave per user finds the hit flag of every rank by binary search in the
 // user's sorted test row, one lane per cut-off sums DCG and IDCG in rank order in fp64; a second,
 // one-workgroup launch adds the users in a fixed order.
@@ -269,6 +274,153 @@ __global__ __launch_bounds__(kTkThreads) void k_score_topk(
   }
 }
 
+// the high word of score_key: larger score -> larger word, +0 above -0 as in the keys
+__device__ __forceinline__ uint32_t score_ord(float v) { return (uint32_t)(score_key(v, 0) >> 32); }
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// gdd_cluster_expand_topk: one wave per user, no workgroup barrier. The user's ranked item clusters
+// (row g of cl_item / cl_score, L entries) are walked in order, 64 at a time into registers (id,
+// score, member range), each cluster's members 64 at a time: a member found in the user's mask row
+// (binary search) is dropped, the first K others are appended with the cluster's score. The walk
+// stops once K appended-or-thresholded members beat the next cluster's score in key order; the
+// mask row's first K items then enter with mask_value, and one select gives the list.
+constexpr int kCxThreads = 256;
+constexpr int kCxUsers = kCxThreads / 64;
+__global__ __launch_bounds__(kCxThreads) void k_cluster_expand_topk(
+    int64_t B, int64_t I, int64_t num_ci, int L, int K, int cap, const int32_t* __restrict__ users, int64_t nu,
+    const int32_t* __restrict__ cl_row, int64_t G, const int32_t* __restrict__ cl_item,
+    const float* __restrict__ cl_score, const int32_t* __restrict__ mem_ptr,
+    const int32_t* __restrict__ mem_item, const int32_t* __restrict__ mask_ptr,
+    const int32_t* __restrict__ mask_col, float mask_value, int32_t* __restrict__ top_item,
+    float* __restrict__ top_score, int32_t* __restrict__ incomplete, int32_t* __restrict__ n_incomplete,
+    int32_t* __restrict__ bad) {
+  extern __shared__ __align__(16) unsigned char cx_smem[];
+  const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
+  const int64_t b = (int64_t)blockIdx.x * kCxUsers + wave;
+  if (b >= B) return;  // wave-uniform
+  uint64_t* buf = reinterpret_cast<uint64_t*>(cx_smem) + (size_t)wave * cap;
+  const uint64_t below = (1ull << lane) - 1ull;
+
+  const int64_t r = users ? (int64_t)users[b] : b;
+  const int64_t g = cl_row[b];
+  bool dead = r < 0 || r >= nu || g < 0 || g >= G;
+  int32_t mp0 = 0, mp1 = 0;
+  if (mask_ptr) {
+    mp0 = mask_ptr[b];
+    mp1 = mask_ptr[b + 1];
+    bool out = false;
+    for (int32_t e = mp0 + lane; e < mp1; e += 64) {
+      const int32_t c = mask_col[e];
+      out |= c < 0 || c >= I;
+    }
+    if (__ballot(out)) dead = true;
+  }
+  const int32_t* ci_row = cl_item + (dead ? 0 : g) * L;
+  const float* cs_row = cl_score + (dead ? 0 : g) * L;
+  if (!dead) {  // a cluster id outside the membership CSR is not dereferenced either
+    bool out = false;
+    for (int t = lane; t < L; t += 64) {
+      const int32_t c = ci_row[t];
+      out |= c < 0 || c >= num_ci;
+    }
+    if (__ballot(out)) dead = true;
+  }
+  if (dead) {
+    for (int t = lane; t < K; t += 64) {
+      top_item[b * K + t] = -1;
+      if (top_score) top_score[b * K + t] = __builtin_nanf("");
+    }
+    if (lane == 0) {
+      incomplete[b] = 0;
+      if (bad) atomicAdd(bad, 1);
+    }
+    return;
+  }
+
+  int cnt = 0;
+  uint64_t thr = 0;
+  int tot = 0;  // unmasked members examined so far, at most K per cluster
+  int gt = 0;   // those of clusters scoring strictly above the current one
+  uint32_t prev = 0;
+  bool complete = false;
+  for (int j0 = 0; j0 < L && !complete; j0 += 64) {
+    const int t = j0 + lane;
+    float s_l = 0.f;
+    uint32_t so_l = 0, nx_l = 0;
+    int32_t mb_l = 0, me_l = 0;
+    if (t < L) {
+      const int32_t c = ci_row[t];
+      s_l = cs_row[t];
+      so_l = score_ord(s_l);
+      nx_l = t + 1 < L ? score_ord(cs_row[t + 1]) : so_l;  // past the list: an unseen cluster may tie the last
+      const int64_t lo = mem_ptr[c], hi = mem_ptr[c + 1];
+      mb_l = (int32_t)(lo < 0 ? 0 : lo > I ? I : lo);  // mem_item holds I entries
+      me_l = (int32_t)(hi < mb_l ? mb_l : hi > I ? I : hi);
+    }
+    const int nb = L - j0 < 64 ? L - j0 : 64;
+    for (int jj = 0; jj < nb; ++jj) {
+      const float s = __int_as_float(uni(__float_as_int(__shfl(s_l, jj))));
+      const uint32_t so = (uint32_t)uni((int)__shfl(so_l, jj)), nx = (uint32_t)uni((int)__shfl(nx_l, jj));
+      const int32_t mb = uni(__shfl(mb_l, jj)), me = uni(__shfl(me_l, jj));
+      if (j0 + jj > 0 && so != prev) gt = tot;
+      prev = so;
+      int taken = 0;
+      for (int32_t e0 = mb; e0 < me && taken < K; e0 += 64) {
+        const int32_t e = e0 + lane;
+        bool ok = e < me;
+        int32_t item = 0;
+        if (ok) {
+          item = mem_item[e];
+          int32_t lo = mp0, hi = mp1;
+          while (lo < hi) {
+            const int32_t mid = (int32_t)(((int64_t)lo + hi) >> 1);
+            if (mask_col[mid] < item) lo = mid + 1; else hi = mid;
+          }
+          ok = !(lo < mp1 && mask_col[lo] == item);
+        }
+        const uint64_t bal = __ballot(ok);
+        const int room = K - taken;
+        const bool take = ok && __popcll(bal & below) < room;  // the cluster's K lowest unmasked ids
+        const int n = __popcll(bal);
+        if (cnt + 64 > cap) wave_select(buf, cap, K, cnt, thr, lane);
+        const uint64_t key = score_key(s, item);
+        const bool cand = take && key > thr;
+        const uint64_t cb = __ballot(cand);
+        if (cand) buf[cnt + __popcll(cb & below)] = key;
+        cnt += __popcll(cb);
+        taken += n < room ? n : room;
+      }
+      tot += taken;
+      if ((so > nx ? tot : gt) >= K) {
+        complete = true;
+        break;
+      }
+    }
+  }
+  if (L == num_ci) complete = true;  // every cluster was seen
+
+  const int nm = mp1 - mp0 < K ? mp1 - mp0 : K;  // the masked items: one score, so the K lowest ids
+  for (int m0 = 0; m0 < nm; m0 += 64) {
+    if (cnt + 64 > cap) wave_select(buf, cap, K, cnt, thr, lane);
+    const int t = m0 + lane;
+    const uint64_t key = t < nm ? score_key(mask_value, mask_col[mp0 + t]) : 0;
+    const bool cand = t < nm && key > thr;
+    const uint64_t cb = __ballot(cand);
+    if (cand) buf[cnt + __popcll(cb & below)] = key;
+    cnt += __popcll(cb);
+  }
+  wave_select(buf, cap, K, cnt, thr, lane);
+  for (int t = lane; t < K; t += 64) {
+    const uint64_t key = buf[t];
+    top_item[b * K + t] = score_key_item(key);
+    if (top_score) top_score[b * K + t] = score_key_value(key);
+  }
+  if (lane == 0) {
+    incomplete[b] = complete ? 0 : 1;
+    if (!complete) atomicAdd(n_incomplete, 1);
+  }
+}
+
 // per_user[b] = (precision, recall, ndcg) x nk of user b's list; one wave per user
 constexpr int kMetThreads = 256;
 __global__ __launch_bounds__(kMetThreads) void k_rank_metrics(
@@ -384,6 +536,34 @@ extern "C" int gdd_score_topk(int64_t B, int64_t I, int d, int K, const int32_t*
   const unsigned grid = (unsigned)((B + kTkUsers - 1) / kTkUsers);
   kern<<<grid, kTkThreads, lds, to_hip(stream)>>>(B, I, d, K, tk_cap(K), users, U, nu, V, mask_ptr, mask_col,
                                                   mask_value, top_item, top_score, bad);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+extern "C" int gdd_cluster_expand_topk(int64_t B, int64_t I, int64_t num_ci, int L, int K, const int32_t* users,
+                                       int64_t nu, const int32_t* cl_row, int64_t G, const int32_t* cl_item,
+                                       const float* cl_score, const int32_t* mem_ptr, const int32_t* mem_item,
+                                       const int32_t* mask_ptr, const int32_t* mask_col, float mask_value,
+                                       int32_t* top_item, float* top_score, int32_t* incomplete,
+                                       int32_t* n_incomplete, int32_t* bad, gdd_stream_t stream) {
+  GDD_REQUIRE(B >= 0 && B < INT32_MAX && I >= 1 && I < INT32_MAX && nu >= 1 && nu < INT32_MAX && G >= 0 &&
+                  G < INT32_MAX,
+              "cluster_expand_topk: B=%lld I=%lld nu=%lld G=%lld unsupported", (long long)B, (long long)I,
+              (long long)nu, (long long)G);
+  GDD_REQUIRE(num_ci >= 1 && num_ci < INT32_MAX && L >= 1 && L <= kTkMaxK && L <= num_ci,
+              "cluster_expand_topk: L=%d outside [1, min(%d, num_ci=%lld)]", L, kTkMaxK, (long long)num_ci);
+  GDD_REQUIRE(K >= 1 && K <= kTkMaxK && K <= I, "cluster_expand_topk: K=%d outside [1, min(%d, I=%lld)]", K,
+              kTkMaxK, (long long)I);
+  if (B == 0) return GDD_OK;
+  GDD_REQUIRE(cl_row && cl_item && cl_score && mem_ptr && mem_item && top_item && incomplete && n_incomplete,
+              "cluster_expand_topk: null pointer");
+  GDD_REQUIRE(!mask_ptr || mask_col, "cluster_expand_topk: mask_ptr without mask_col");
+  const int cap = tk_cap(K);
+  const size_t lds = sizeof(uint64_t) * kCxUsers * (size_t)cap;  // at most 16 KiB
+  const unsigned grid = (unsigned)((B + kCxUsers - 1) / kCxUsers);
+  k_cluster_expand_topk<<<grid, kCxThreads, lds, to_hip(stream)>>>(
+      B, I, num_ci, L, K, cap, users, nu, cl_row, G, cl_item, cl_score, mem_ptr, mem_item, mask_ptr, mask_col,
+      mask_value, top_item, top_score, incomplete, n_incomplete, bad);
   GDD_LAUNCHED();
   return GDD_OK;
 }

@@ -25,6 +25,10 @@ the reference file:line each entry point replaces):
 * :mod:`gdd.rankeval` — :func:`recommend` (ranked top-K lists from a fused score + top-K kernel that
   never writes a score), :func:`rank_metrics` and :class:`RankingEvaluator` (precision, recall and
   NDCG@K as the reference teacher computes them)
+* :mod:`gdd.condrank` — :func:`recommend_condensed` / :class:`CondensedRecommender`: the same lists
+  from a condensed recommender's cluster tables and maps without expanding them (clusters ranked
+  once per user cluster, expanded per user); ``python -m gdd.recommend_distilled`` serves the saved
+  artefact
 * :mod:`gdd.agent` / :mod:`gdd.agent_induct` — the transductive and inductive ClustGDD agents;
   :mod:`gdd.train_clustgdd_transduct` / :mod:`gdd.train_clustgdd_induct` /
   :mod:`gdd.distill_recsys` — the drop-in command lines
@@ -32,6 +36,7 @@ the reference file:line each entry point replaces):
 from . import _lib  # noqa: F401  (imports torch first, see _lib docstring)
 from . import gcn, pipeline, rankeval, rankformer, recsys  # noqa: F401
 from .cluster import argmax_rows, cluster_mean, group_by_label
+from .condrank import CondensedRecommender, recommend_condensed
 from .condense import ER_estimator, attaw_ER_estimator, graph_compress, graph_sparse
 from .graph import (CSRGraph, induced_subgraph, normalize_adj, normalize_adj_tensor, propagate, spmm,
                     to_csr)
@@ -47,5 +52,5 @@ __all__ = [
     "induced_subgraph", "group_by_label", "graph_sparse", "graph_compress", "ER_estimator", "attaw_ER_estimator",
     "truncated_svd", "svd_embeddings",
     "InteractionGraph", "RankformerLayer", "GCNLayer", "RankformerTeacher", "save_teacher",
-    "recommend", "rank_metrics", "RankingEvaluator",
+    "recommend", "rank_metrics", "RankingEvaluator", "recommend_condensed", "CondensedRecommender",
 ]

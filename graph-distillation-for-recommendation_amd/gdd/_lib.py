@@ -176,6 +176,8 @@ SIGNATURES = {
                                _vp, _vp, _vp, _c_size, _vp]),
     "gdd_score_topk": (_c_int, [_c_i64, _c_i64, _c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_f32, _vp,
                                 _vp, _vp, _vp]),
+    "gdd_cluster_expand_topk": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _c_f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdd_rank_metrics": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdd_infonce_ws_bytes": (_c_size, [_c_i64, _c_int]),
     "gdd_infonce_rows": (_c_int, [_c_i64, _c_int, _vp, _vp, _c_f32, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),

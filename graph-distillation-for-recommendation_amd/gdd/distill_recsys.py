@@ -23,7 +23,9 @@ Stage by stage (reference line ranges):
 ``--report_ranking`` (not in the reference; without it stdout is the reference's) adds, after the
 refinement, NDCG / recall / precision of the refined condensed model over the evaluated test users
 by :class:`gdd.rankeval.RankingEvaluator`, and with ``--teacher_path`` the same for the teacher's raw
-embeddings.
+embeddings. With ``--report_from_clusters`` the condensed model's lines are computed from its cluster
+tables (:mod:`gdd.condrank`) without expanding them; the lines are the same. The saved artefact is
+served by :mod:`gdd.recommend_distilled`.
 
 The reference falls back to the CPU when no GPU is visible; this driver has no CPU path.
 """
@@ -142,6 +144,9 @@ def parse_args(argv=None):
                    help="after refinement print NDCG / recall / precision at --report_topks of the refined "
                         "condensed model (and of the teacher's raw embeddings) over the evaluated test users")
     p.add_argument("--report_topks", type=str, default=None, help="cut-offs of --report_ranking (default: [eval_topk])")
+    p.add_argument("--report_from_clusters", action="store_true",
+                   help="with --report_ranking: rank the condensed model from its cluster tables "
+                        "(gdd.condrank) instead of expanding them to every user and item; the same lines")
     return p.parse_args(argv)
 
 
@@ -268,7 +273,10 @@ def run(args, out_root: str = "ClustGDD", embeddings=None, timings: Optional[dic
         model.eval()
         with torch.no_grad():
             cu_z, ci_z = model.propagate()
-            m = ranking(cu_z[u2cu_t], ci_z[i2ci_t])
+            if getattr(args, "report_from_clusters", False):
+                m = ranking.condensed(cu_z, ci_z, u2cu, i2ci)
+            else:
+                m = ranking(cu_z[u2cu_t], ci_z[i2ci_t])
         for line in format_metrics(topks, m):
             print(f"[rank] condensed ({m['users']} users): {line}")
         if args.teacher_path is not None:

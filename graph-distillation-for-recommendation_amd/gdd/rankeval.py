@@ -9,7 +9,8 @@
 * :class:`RankingEvaluator` — both with the host preparation done once, the counterpart of
   :class:`gdd.recsys.RecallEvaluator` for the reference teacher's three metrics. Recall here is
   ``hits / min(n, k)`` averaged over users (model.py:43-47), not the driver's micro
-  ``hits / total``.
+  ``hits / total``. ``RankingEvaluator.condensed`` evaluates a condensed model from its cluster
+  tables (:mod:`gdd.condrank`): the same lists, so the same numbers.
 
 Argument errors raise ``ValueError`` before the device is touched. There is no CPU path.
 """
@@ -281,6 +282,30 @@ class RankingEvaluator:
         if n_bad:
             g["out"][-1:].zero_()
             _raise_bad(n_bad)
+        count = int(host[3 * nk:3 * nk + 1].view(torch.int64)[0])
+        means = host[:3 * nk].view(3, nk).numpy() / max(count, 1)
+        return {"precision": means[0].copy(), "recall": means[1].copy(), "ndcg": means[2].copy(),
+                "users": count}
+
+    @torch.no_grad()
+    def condensed(self, cu_z: torch.Tensor, ci_z: torch.Tensor, u2cu, i2ci) -> dict:
+        """What ``self(cu_z[u2cu], ci_z[i2ci])`` returns, from the condensed model itself: the lists of
+        :class:`gdd.condrank.CondensedRecommender` (the same items, so the same metrics) and
+        ``gdd_rank_metrics``."""
+        from .condrank import CondensedRecommender, _distinct_columns
+        rec =CondensedRecommender(cu_z, ci_z, u2cu, i2ci)
+        if rec.num_users != self.num_users or rec.num_items != self.num_items:
+            raise ValueError(f"cluster maps of {rec.num_users} users x {rec.num_items} items for an evaluator "
+                             f"of {self.num_users} x {self.num_items}")
+        nk = len(self.topks)
+        if self.users.size == 0:
+            z = np.zeros(nk)
+            return {"precision": z.copy(), "recall": z.copy(), "ndcg": z.copy(), "users": 0}
+        g = self._prepare()
+        items, _ = rec._lists(self.k, self.users, _distinct_columns(*self._host[0]), self.mask_value, False)
+        _rank_metrics(_lib.device_lib(), items, g["te_ptr"], g["te_col"], g["deg"], g["tk"], g["inv"], nk,
+                      g["out"])
+        host = g["out"].cpu()
         count = int(host[3 * nk:3 * nk + 1].view(torch.int64)[0])
         means = host[:3 * nk].view(3, nk).numpy() / max(count, 1)
         return {"precision": means[0].copy(), "recall": means[1].copy(), "ndcg": means[2].copy(),

@@ -226,6 +226,25 @@ class _BiMessage(torch.autograd.Function):
         return d_norm, d_u, d_it, None
 
 
+def lightgcn_propagate(u0: torch.Tensor, i0: torch.Tensor, w: torch.Tensor, edge_index: torch.Tensor,
+                       graph: _Bipartite, num_layers: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The body of ``LightGCNCondensed.propagate`` (:323-350) as a function of the layer-0 tables, the
+    edge weights and the graph: symmetric normalisation by the weighted degrees, ``num_layers``
+    message-passing layers, the mean over the layers. Also what
+    :meth:`gdd.condrank.CondensedRecommender.load` runs on the saved artefact."""
+    cu, ci = edge_index[0], edge_index[1]
+    deg_u = torch.zeros(graph.num_cu, device=w.device).index_add_(0, cu, w)
+    deg_i = torch.zeros(graph.num_ci, device=w.device).index_add_(0, ci, w)
+    norm = w / (torch.sqrt(deg_u[cu] + 1e-8) * torch.sqrt(deg_i[ci] + 1e-8))
+    u, it = u0, i0
+    u_layers, i_layers = [u], [it]
+    for _ in range(int(num_layers)):
+        u, it = _BiMessage.apply(norm, u, it, graph)
+        u_layers.append(u)
+        i_layers.append(it)
+    return torch.stack(u_layers, dim=0).mean(dim=0), torch.stack(i_layers, dim=0).mean(dim=0)
+
+
 class LightGCNCondensed(nn.Module):
     """distill_recsys.LightGCNCondensed (:275-384) with the message passing on libgdd."""
 
@@ -258,19 +277,7 @@ class LightGCNCondensed(nn.Module):
     def propagate(self) -> Tuple[torch.Tensor, torch.Tensor]:
         u0 = self.user_emb.weight + self.user_delta
         i0 = self.item_emb.weight + self.item_delta
-        cu, ci = self.edge_index[0], self.edge_index[1]
-        w = self.edge_weight()
-        deg_u = torch.zeros(self.num_cu, device=w.device).index_add_(0, cu, w)
-        deg_i = torch.zeros(self.num_ci, device=w.device).index_add_(0, ci, w)
-        norm = w / (torch.sqrt(deg_u[cu] + 1e-8) * torch.sqrt(deg_i[ci] + 1e-8))
-        g = self.graph()
-        u, it = u0, i0
-        u_layers, i_layers = [u], [it]
-        for _ in range(self.num_layers):
-            u, it = _BiMessage.apply(norm, u, it, g)
-            u_layers.append(u)
-            i_layers.append(it)
-        return torch.stack(u_layers, dim=0).mean(dim=0), torch.stack(i_layers, dim=0).mean(dim=0)
+        return lightgcn_propagate(u0, i0, self.edge_weight(), self.edge_index, self.graph(), self.num_layers)
 
     def bpr_loss(self, u: torch.Tensor, pos_i: torch.Tensor, neg_i: torch.Tensor,
                  reg_lambda: float = 1e-4) -> torch.Tensor:

@@ -720,6 +720,30 @@ int gdd_rank_wsum(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* ro
 /*   [0, nu) or a mask column outside [0, I) is not dereferenced: *bad (device int, nullable, not    */
 /*   cleared here) is incremented once for that row and the row is all -1 (top_score NaN). No score  */
 /*   is written to memory, no workspace, no floating-point atomics: two runs give the same bits.     */
+/* gdd_cluster_expand_topk (model.py:304-317 for a condensed model, DESIGN.md "Top-K from the        */
+/*   condensed model"): the lists gdd_score_topk gives on the expanded tables U[b] = cu_z[u2cu[b]],  */
+/*   V[i] = ci_z[i2ci[i]], from a ranking of the item clusters. cl_item / cl_score (G x L) are the   */
+/*   output of gdd_score_topk(G, num_ci, d, L, the G distinct user clusters, cu_z, num_cu, ci_z, no  */
+/*   mask, scores) with L = min(num_ci, 256) (1 <= L <= 256, L <= num_ci): row g lists the best L    */
+/*   item clusters of one user cluster, descending in key order, with the exact score bits.          */
+/*   For b < B: r = users[b] (users NULL: r = b; used for the range check alone), cl_row[b] the row  */
+/*   of cl_* of the user's cluster, mem_ptr [num_ci + 1] / mem_item [I] the members of every item    */
+/*   cluster in ascending item id (each item in exactly one cluster; empty clusters allowed),        */
+/*   mask_ptr / mask_col, mask_value, K, top_item, top_score and bad as in gdd_score_topk, the mask  */
+/*   columns of a row strictly ascending. 1 <= K <= 256, K <= I < 2^31.                              */
+/*   The clusters c_0 .. c_{L-1} of the row are walked in order. Of cluster c_j the unmasked         */
+/*   members (binary search in the mask row) with the K lowest ids enter with score s_j = cl_score;  */
+/*   the first min(K, row length) items of the mask row enter with mask_value; the K largest keys    */
+/*   are the list. The walk stops after the first j at which K entered-or-thresholded members of     */
+/*   c_0 .. c_j score strictly above s_{j+1} (key order; past the row, s_L = s_{L-1}: an unseen      */
+/*   cluster may tie the last one): they beat every item not examined. A row whose walk ends without */
+/*   that, with L < num_ci, is incomplete: incomplete[b] = 1 (else 0; B ints, written for every b)   */
+/*   and *n_incomplete (device int, not cleared here) is incremented; its list is to be recomputed   */
+/*   by gdd_score_topk on V = ci_z[i2ci]. With L == num_ci no row is incomplete.                     */
+/*   A user id outside [0, nu), a cl_row outside [0, G), a cluster id of the row outside [0, num_ci) */
+/*   or a mask column outside [0, I) is not dereferenced: the row is all -1 (top_score NaN), *bad is */
+/*   incremented once and incomplete[b] = 0. mem_ptr values are clamped to [0, I]. No score matrix,  */
+/*   no workspace, integer atomics on the two counters only: two runs give the same bits.            */
 /* gdd_rank_metrics (model.py:27-53): per user b with n = te_deg[b] (te_deg NULL: the row length;     */
 /*   the reference counts repeated lines of the split, dataloader.py:65-70) and per cut-off          */
 /*   k = topks[j] (device, nk <= 8 ascending values in [1, K]; an entry outside is clamped):         */
@@ -734,6 +758,12 @@ int gdd_rank_wsum(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* ro
 int gdd_score_topk(int64_t B, int64_t I, int d, int K, const int32_t* users, const float* U, int64_t nu,
                    const float* V, const int32_t* mask_ptr, const int32_t* mask_col, float mask_value,
                    int32_t* top_item, float* top_score, int32_t* bad, gdd_stream_t stream);
+int gdd_cluster_expand_topk(int64_t B, int64_t I, int64_t num_ci, int L, int K, const int32_t* users,
+                            int64_t nu, const int32_t* cl_row, int64_t G, const int32_t* cl_item,
+                            const float* cl_score, const int32_t* mem_ptr, const int32_t* mem_item,
+                            const int32_t* mask_ptr, const int32_t* mask_col, float mask_value,
+                            int32_t* top_item, float* top_score, int32_t* incomplete, int32_t* n_incomplete,
+                            int32_t* bad, gdd_stream_t stream);
 int gdd_rank_metrics(int64_t B, int K, const int32_t* top_item, const int32_t* te_ptr, const int32_t* te_col,
                      const int32_t* te_deg, int nk, const int32_t* topks, const double* inv_log2,
                      double* per_user, double* sums, int64_t* count, gdd_stream_t stream);
