@@ -25,6 +25,11 @@
 // gdd_rank_metrics: one wave per user finds the hit flag of every rank by binary search in the
 // user's sorted test row, one lane per cut-off sums DCG and IDCG in rank order in fp64; a second,
 // one-workgroup launch adds the users in a fixed order.
+//
+// gdd_score_positions / gdd_cluster_positions: for given (user, item) pairs the number of items
+// whose key is above the item's, i.e. its index in the full ranked list, with k_score_topk's tiling
+// (k_score_positions) or from the cluster tables of a condensed model (k_cluster_scores,
+// k_cluster_positions); see "Full-ranking positions" below.
 #include <climits>
 
 #include "gdd_common.hpp"
@@ -421,6 +426,509 @@ __global__ __launch_bounds__(kCxThreads) void k_cluster_expand_topk(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Full-ranking positions: pos(b, t) = #{ i : key(b, i) > key(b, t) } for the targets of a CSR.
+//
+// k_score_positions keeps k_score_topk's tiling (16 users per workgroup, four per wave, 64-item
+// tiles staged once, user rows through scalar loads, the same fmaf chain). A user's targets are
+// taken kRpChunk at a time; per chunk
+//   * pre-pass: one lane per target computes the target's own key with the same chain (its row of V
+//     gathered from memory), the masked flag by binary search in the mask row; the wave sorts the
+//     keys descending (bitonic) with the target's place in the chunk as payload;
+//   * streaming pass over all items: each lane counts by binary search the targets whose key is not
+//     below its item's key, p, and adds one to integer bucket p in LDS (the item ranks above the
+//     sorted targets p, p + 1, ...); an item at or below every target adds nothing;
+//   * the inclusive prefix sum of the buckets is the position of each sorted target.
+// The wave owns its users: LDS integer atomics between its own lanes, no float atomics, no
+// workspace. A workgroup passes over V once per chunk of its longest row.
+// ---------------------------------------------------------------------------------------------
+constexpr int kRpChunk = 256;  // targets of one user per pass over the items; the payload is a byte
+
+inline size_t rp_lds(int d) {
+  return (sizeof(uint64_t) + sizeof(int32_t) + sizeof(uint8_t)) * (size_t)kTkUsers * kRpChunk +
+         sizeof(float) * (size_t)kTkItems * tk_stride(d) + sizeof(int32_t) * (kTkThreads + 2 * kTkUsers);
+}
+
+// bitonic sort of key[0 .. cap) (cap a power of two >= 2), descending, idx carried along; one wave
+__device__ __forceinline__ void wave_sort_desc_idx(uint64_t* key, uint8_t* idx, int cap, int lane) {
+  for (int k = 2; k <= cap; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = lane; t < (cap >> 1); t += 64) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const int p = i | j;
+        const uint64_t a = key[i], b = key[p];
+        const bool swap = (i & k) == 0 ? a < b : a > b;
+        if (swap) {
+          key[i] = b;
+          key[p] = a;
+          const uint8_t x = idx[i];
+          idx[i] = idx[p];
+          idx[p] = x;
+        }
+      }
+      wave_sync();
+    }
+  }
+}
+
+// whether item is in the ascending row col[lo .. hi)
+__device__ __forceinline__ bool row_has(const int32_t* __restrict__ col, int32_t lo, int32_t hi, int32_t item) {
+  const int32_t end = hi;
+  while (lo < hi) {
+    const int32_t mid = (int32_t)(((int64_t)lo + hi) >> 1);
+    if (col[mid] < item) lo = mid + 1; else hi = mid;
+  }
+  return lo < end && col[lo] == item;
+}
+
+template <int NP>
+__global__ __launch_bounds__(kTkThreads) void k_score_positions(
+    int64_t B, int64_t I, int d, const int32_t* __restrict__ users, const float* __restrict__ U, int64_t nu,
+    const float* __restrict__ V, const int32_t* __restrict__ mask_ptr, const int32_t* __restrict__ mask_col,
+    float mask_value, const int32_t* __restrict__ tg_ptr, const int32_t* __restrict__ tg_col,
+    int32_t* __restrict__ pos, int32_t* __restrict__ bad) {
+  extern __shared__ __align__(16) unsigned char rp_smem[];
+  const int S = tk_stride(d);
+  uint64_t* s_keys = reinterpret_cast<uint64_t*>(rp_smem);                     // kTkUsers x kRpChunk
+  float* s_v = reinterpret_cast<float*>(s_keys + (size_t)kTkUsers * kRpChunk);  // kTkItems x S
+  int32_t* s_cnt = reinterpret_cast<int32_t*>(s_v + kTkItems * S);              // kTkUsers x kRpChunk
+  int32_t* s_flag = s_cnt + kTkUsers * kRpChunk;                               // one per thread
+  int32_t* s_row = s_flag + kTkThreads;                                        // U row of each user, -1: none
+  int32_t* s_len = s_row + kTkUsers;                                           // targets of each user to rank
+  uint8_t* s_idx = reinterpret_cast<uint8_t*>(s_len + kTkUsers);               // kTkUsers x kRpChunk
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b0 = (int64_t)blockIdx.x * kTkUsers;
+
+  if (tid < kTkUsers) {
+    const int64_t b = b0 + tid;
+    int32_t row = -1;
+    if (b < B) {
+      const int64_t r = users ? (int64_t)users[b] : b;
+      if (r >= 0 && r < nu) row = (int32_t)r;
+    }
+    s_row[tid] = row;
+  }
+  __syncthreads();
+
+  // the wave's users: mask and target rows, checked once (a column outside [0, I) kills the row)
+  bool live[kTkUW];
+  int32_t mb[kTkUW], cur[kTkUW], end[kTkUW], tb[kTkUW], tn[kTkUW];
+  int64_t nxt[kTkUW];  // the mask column at cur (wave-uniform), INT64_MAX past the row's end
+#pragma unroll
+  for (int j = 0; j < kTkUW; ++j) {
+    const int ul = wave * kTkUW + j;
+    const int64_t b = b0 + ul;
+    live[j] = b < B;
+    bool dead = live[j] && s_row[ul] < 0;
+    mb[j] = cur[j] = end[j] = tb[j] = tn[j] = 0;
+    nxt[j] = INT64_MAX;
+    if (live[j]) {
+      bool out = false;
+      if (mask_ptr) {
+        mb[j] = mask_ptr[b];
+        end[j] = mask_ptr[b + 1];
+        for (int32_t e = mb[j] + lane; e < end[j]; e += 64) {
+          const int32_t c = mask_col[e];
+          out |= c < 0 || c >= I;
+        }
+      }
+      tb[j] = tg_ptr[b];
+      const int32_t te = tg_ptr[b + 1];
+      tn[j] = te > tb[j] ? te - tb[j] : 0;
+      for (int32_t e = lane; e < tn[j]; e += 64) {
+        const int32_t c = tg_col[tb[j] + e];
+        out |= c < 0 || c >= I;
+      }
+      if (__ballot(out)) dead = true;
+      if (dead) {
+        for (int32_t e = lane; e < tn[j]; e += 64) pos[tb[j] + e] = -1;
+        if (bad && lane == 0) atomicAdd(bad, 1);
+        live[j] = false;
+      }
+    }
+    if (lane == 0) s_len[ul] = live[j] ? tn[j] : 0;
+  }
+  __syncthreads();
+  int maxlen = 0;
+#pragma unroll
+  for (int u = 0; u < kTkUsers; ++u) maxlen = s_len[u] > maxlen ? s_len[u] : maxlen;
+
+  const float* vrow = s_v + lane * S;
+  const float* ug[kTkUW];
+#pragma unroll
+  for (int j = 0; j < kTkUW; ++j) {
+    const int32_t row = __builtin_amdgcn_readfirstlane(s_row[__builtin_amdgcn_readfirstlane(wave) * kTkUW + j]);
+    ug[j] = U + (int64_t)(row >= 0 ? row : 0) * d;  // no valid row: never ranked (live is false)
+  }
+  const int d4 = d & ~3;
+  const int q = d >> 2;  // float4 per row
+  f32x4 pre[NP > 0 ? NP : 1];
+  int pre_off[NP > 0 ? NP : 1];
+  if (NP > 0) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int idx = tid + p * kTkThreads, r = idx / q;
+      pre_off[p] = r * S + 4 * (idx - r * q);
+    }
+  }
+
+  for (int c0 = 0; c0 < maxlen; c0 += kRpChunk) {  // uniform over the workgroup
+    int n[kTkUW], capn[kTkUW];
+#pragma unroll
+    for (int j = 0; j < kTkUW; ++j) {
+      const int ul = wave * kTkUW + j;
+      n[j] = 0;
+      capn[j] = 2;
+      if (live[j] && tn[j] > c0) n[j] = tn[j] - c0 < kRpChunk ? tn[j] - c0 : kRpChunk;
+      if (n[j] == 0) continue;  // wave-uniform
+      while (capn[j] < n[j]) capn[j] <<= 1;
+      uint64_t* keys = s_keys + ul * kRpChunk;
+      for (int i = lane; i < capn[j]; i += 64) {
+        uint64_t key = 0;  // below every key
+        if (i < n[j]) {
+          const int32_t t = tg_col[tb[j] + c0 + i];
+          const float* v = V + (int64_t)t * d;
+          float a = 0.f;
+          for (int f = 0; f < d; ++f) a = __builtin_fmaf(ug[j][f], v[f], a);
+          key = score_key(row_has(mask_col, mb[j], end[j], t) ? mask_value : a, t);
+        }
+        keys[i] = key;
+        s_idx[ul * kRpChunk + i] = (uint8_t)i;
+        s_cnt[ul * kRpChunk + i] = 0;
+      }
+      wave_sync();
+      wave_sort_desc_idx(keys, s_idx + ul * kRpChunk, capn[j], lane);
+      cur[j] = mb[j];
+      nxt[j] = cur[j] < end[j] ? (int64_t)mask_col[cur[j]] : (int64_t)INT64_MAX;
+    }
+
+    if (NP > 0) tk_fetch<NP>(pre, V, (int)(I < kTkItems ? I : kTkItems) * q, tid);
+    for (int64_t i0 = 0; i0 < I; i0 += kTkItems) {
+      const int rows = (int)(I - i0 < kTkItems ? I - i0 : kTkItems);
+      __syncthreads();  // the previous tile has been scored
+      if (NP > 0) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+          if (tid + p * kTkThreads < rows * q) *reinterpret_cast<f32x4*>(s_v + pre_off[p]) = pre[p];
+        if (i0 + kTkItems < I) {
+          const int64_t left = I - i0 - kTkItems;
+          tk_fetch<NP>(pre, V + (i0 + kTkItems) * d, (int)(left < kTkItems ? left : kTkItems) * q, tid);
+        }
+      } else {
+        const float* src = V + i0 * d;
+        for (int idx = tid; idx < rows * d; idx += kTkThreads) {
+          const int r = idx / d, f = idx - r * d;
+          s_v[r * S + f] = src[idx];
+        }
+      }
+      __syncthreads();
+      const int64_t item = i0 + lane;
+      const int64_t tile_end = i0 + kTkItems;
+      float acc[kTkUW];
+#pragma unroll
+      for (int j = 0; j < kTkUW; ++j) acc[j] = 0.f;
+      if (lane < rows) {
+        for (int f = 0; f < d4; f += 4) {
+          const float4 v = *reinterpret_cast<const float4*>(vrow + f);
+#pragma unroll
+          for (int j = 0; j < kTkUW; ++j) {
+            const float* u = ug[j] + f;
+            float a = acc[j];
+            a = __builtin_fmaf(u[0], v.x, a);
+            a = __builtin_fmaf(u[1], v.y, a);
+            a = __builtin_fmaf(u[2], v.z, a);
+            a = __builtin_fmaf(u[3], v.w, a);
+            acc[j] = a;
+          }
+        }
+        for (int f = d4; f < d; ++f) {
+          const float v = vrow[f];
+#pragma unroll
+          for (int j = 0; j < kTkUW; ++j) acc[j] = __builtin_fmaf(ug[j][f], v, acc[j]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kTkUW; ++j) {
+        if (n[j] == 0) continue;  // wave-uniform
+        const int ul = wave * kTkUW + j;
+        bool masked = false;
+        if (nxt[j] < tile_end) {  // wave-uniform
+          s_flag[tid] = 0;
+          wave_sync();
+          for (;;) {
+            const int32_t e = cur[j] + lane;
+            const int64_t c = e < end[j] ? (int64_t)mask_col[e] : (int64_t)INT64_MAX;
+            const bool in = c < tile_end;
+            if (in && c >= i0) s_flag[wave * 64 + (int)(c - i0)] = 1;
+            const int m = __popcll(__ballot(in));
+            cur[j] += m;
+            if (m < 64) break;
+          }
+          wave_sync();
+          masked = s_flag[tid] != 0;
+          wave_sync();
+          nxt[j] = cur[j] < end[j] ? (int64_t)mask_col[cur[j]] : (int64_t)INT64_MAX;
+        }
+        if (lane < rows) {
+          const uint64_t key = score_key(masked ? mask_value : acc[j], item);
+          const uint64_t* keys = s_keys + ul * kRpChunk;
+          int p = 0;  // the sorted targets at or above this item's key
+          for (int s = capn[j] >> 1; s > 0; s >>= 1)
+            if (keys[p + s - 1] >= key) p += s;
+          if (keys[p] >= key) ++p;
+          if (p < n[j]) atomicAdd(&s_cnt[ul * kRpChunk + p], 1);
+        }
+      }
+    }
+
+#pragma unroll
+    for (int j = 0; j < kTkUW; ++j) {
+      if (n[j] == 0) continue;
+      const int ul = wave * kTkUW + j;
+      wave_sync();
+      int carry = 0;
+      for (int seg = 0; seg < n[j]; seg += 64) {
+        const int i = seg + lane;
+        int v = i < n[j] ? s_cnt[ul * kRpChunk + i] : 0;
+        for (int o = 1; o < 64; o <<= 1) {
+          const int up = __shfl_up(v, o);
+          if (lane >= o) v += up;
+        }
+        v += carry;
+        if (i < n[j]) pos[tb[j] + c0 + (int)s_idx[ul * kRpChunk + i]] = v;
+        carry = __shfl(v, 63);
+      }
+      wave_sync();  // the next chunk's pre-pass overwrites the buckets
+    }
+  }
+}
+
+// S[g, c] = the chain score of user cluster groups[g] against item cluster c (G x num_ci): lane =
+// item cluster, four user clusters per wave through scalar loads. A group outside [0, num_cu) is
+// not read (its row is zeros; k_cluster_positions drops the users of such a row).
+constexpr int kCsGroups = 16;
+__global__ __launch_bounds__(256) void k_cluster_scores(int64_t G, int64_t num_cu, int64_t num_ci, int d,
+                                                        int64_t n_ctiles, const int32_t* __restrict__ groups,
+                                                        const float* __restrict__ cu_z,
+                                                        const float* __restrict__ ci_z, float* __restrict__ S) {
+  const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
+  const int64_t gt = blockIdx.x / n_ctiles, ct = blockIdx.x - gt * n_ctiles;
+  const int64_t c = ct * 64 + lane;
+  const int64_t g0 = gt * kCsGroups + wave * 4;
+  const float* ug[4];
+  bool ok[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int64_t r = g0 + j < G ? (int64_t)groups[g0 + j] : -1;
+    ok[j] = r >= 0 && r < num_cu;
+    ug[j] = cu_z + (ok[j] ? r : 0) * d;
+  }
+  if (c >= num_ci) return;
+  const float* v = ci_z + c * d;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int f = 0; f < d; ++f) {
+    const float x = v[f];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(ug[j][f], x, acc[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (g0 + j < G) S[(g0 + j) * num_ci + c] = ok[j] ? acc[j] : 0.f;
+}
+
+// the member range of item cluster c in mem_item (I entries), clamped
+__device__ __forceinline__ void mem_range(const int32_t* __restrict__ mem_ptr, int64_t c, int64_t I, int32_t& lo,
+                                          int32_t& hi) {
+  const int64_t lo64 = mem_ptr[c], hi64 = mem_ptr[c + 1];
+  lo = (int32_t)(lo64 < 0 ? 0 : lo64 > I ? I : lo64);
+  hi = (int32_t)(hi64 < lo ? lo : hi64 > I ? I : hi64);
+}
+// the members mem_item[lo .. hi) (ascending) with an id below t
+__device__ __forceinline__ int members_below(const int32_t* __restrict__ mem_item, int32_t lo, int32_t hi,
+                                             int32_t t) {
+  int32_t a = lo, z = hi;
+  while (a < z) {
+    const int32_t mid = (int32_t)(((int64_t)a + z) >> 1);
+    if (mem_item[mid] < t) a = mid + 1; else z = mid;
+  }
+  return a - lo;
+}
+// a masked item mi whose cluster scores om: counted where mask_value puts it, not where its cluster did
+__device__ __forceinline__ int mask_shift(uint32_t omv, uint32_t om, uint32_t ot, int32_t mi, int32_t t) {
+  const bool as_masked = omv > ot || (omv == ot && mi < t);
+  const bool as_member = om > ot || (om == ot && mi < t);
+  return (int)as_masked - (int)as_member;
+}
+
+// Row g of the score table in ranked order, once per user cluster: sc[g, k] is the item cluster at
+// place k (descending score word, ties by ascending cluster id), pre[g, k] the members of the
+// clusters before place k (num_ci + 1 entries). One workgroup per row, a bitonic sort of at most
+// kCpSortMax keys in LDS, then a block scan of the sizes.
+constexpr int kCpSortMax = 4096;  // 32 KiB of keys
+constexpr int kCpThreads = 256;
+__global__ __launch_bounds__(kCpThreads) void k_cluster_rank_rows(int64_t I, int num_ci, int cap,
+                                                                  const float* __restrict__ S,
+                                                                  const int32_t* __restrict__ mem_ptr,
+                                                                  int32_t* __restrict__ sc, int32_t* __restrict__ pre) {
+  extern __shared__ __align__(16) unsigned char cp_smem[];
+  __shared__ int32_t s_part[kCpThreads];
+  uint64_t* keys = reinterpret_cast<uint64_t*>(cp_smem);  // cap
+  const int tid = threadIdx.x;
+  const int64_t g = blockIdx.x;
+  const float* srow = S + g * num_ci;
+  for (int c = tid; c < cap; c += kCpThreads) keys[c] = c < num_ci ? score_key(srow[c], c) : 0;  // 0: below every key
+  __syncthreads();
+  for (int k = 2; k <= cap; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (cap >> 1); t += kCpThreads) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const int p = i | j;
+        const uint64_t a = keys[i], b = keys[p];
+        const bool swap = (i & k) == 0 ? a < b : a > b;
+        if (swap) {
+          keys[i] = b;
+          keys[p] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const int per = (num_ci + kCpThreads - 1) / kCpThreads;  // consecutive places per thread
+  const int k0 = tid * per < num_ci ? tid * per : num_ci;
+  const int k1 = k0 + per < num_ci ? k0 + per : num_ci;
+  int sum = 0;
+  for (int k = k0; k < k1; ++k) {
+    int32_t lo, hi;
+    mem_range(mem_ptr, score_key_item(keys[k]), I, lo, hi);
+    sum += hi - lo;
+  }
+  s_part[tid] = sum;
+  __syncthreads();
+  int base = 0;
+  for (int i = 0; i < tid; ++i) base += s_part[i];
+  for (int k = k0; k < k1; ++k) {
+    const int32_t c = score_key_item(keys[k]);
+    int32_t lo, hi;
+    mem_range(mem_ptr, c, I, lo, hi);
+    sc[g * num_ci + k] = c;
+    pre[g * (num_ci + 1) + k] = base;
+    base += hi - lo;
+    if (k == num_ci - 1) pre[g * (num_ci + 1) + num_ci] = base;
+  }
+}
+
+// gdd_cluster_positions: one wave per user. With o_t the score word of the target (mask_value's if
+// it is masked, else its cluster's): a cluster above o_t adds its size, a cluster at o_t its members
+// below t (binary search in mem_item), and each item of the mask row is counted where mask_value puts
+// it instead of where its cluster did.
+//   RANKED (num_ci <= kCpSortMax, rows ranked by k_cluster_rank_rows): one lane per target. The
+//   clusters above o_t are a prefix of the ranked row, found by binary search, and their sizes one
+//   entry of pre; only the tied clusters that follow and the mask row are walked.
+//   Otherwise: one target after the other, the lanes over all clusters and then over the mask row,
+//   with an integer wave sum.
+template <bool RANKED>
+__global__ __launch_bounds__(kCxThreads) void k_cluster_positions(
+    int64_t B, int64_t I, int64_t num_cu, int64_t num_ci, const int32_t* __restrict__ users, int64_t nu,
+    const int32_t* __restrict__ cl_row, int64_t G, const int32_t* __restrict__ groups,
+    const float* __restrict__ S, const int32_t* __restrict__ sc, const int32_t* __restrict__ pre,
+    const int32_t* __restrict__ i2ci, const int32_t* __restrict__ mem_ptr,
+    const int32_t* __restrict__ mem_item, const int32_t* __restrict__ mask_ptr,
+    const int32_t* __restrict__ mask_col, float mask_value, const int32_t* __restrict__ tg_ptr,
+    const int32_t* __restrict__ tg_col, int32_t* __restrict__ pos, int32_t* __restrict__ bad) {
+  const int lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
+  const int64_t b = (int64_t)blockIdx.x * kCxUsers + wave;
+  if (b >= B) return;  // wave-uniform
+
+  const int64_t r = users ? (int64_t)users[b] : b;
+  const int64_t g = cl_row[b];
+  bool dead = r < 0 || r >= nu || g < 0 || g >= G;
+  if (!dead) {
+    const int64_t gr = groups[g];
+    dead = gr < 0 || gr >= num_cu;
+  }
+  int32_t mp0 = 0, mp1 = 0;
+  bool out = false;
+  if (mask_ptr) {  // an item id outside [0, I) or an item's cluster outside [0, num_ci) kills the row
+    mp0 = mask_ptr[b];
+    mp1 = mask_ptr[b + 1];
+    for (int32_t e = mp0 + lane; e < mp1; e += 64) {
+      const int32_t c = mask_col[e];
+      bool o = c < 0 || c >= I;
+      if (!o) {
+        const int32_t k = i2ci[c];
+        o = k < 0 || k >= num_ci;
+      }
+      out |= o;
+    }
+  }
+  const int32_t tb = tg_ptr[b];
+  const int32_t te = tg_ptr[b + 1] > tb ? tg_ptr[b + 1] : tb;
+  for (int32_t e = tb + lane; e < te; e += 64) {
+    const int32_t c = tg_col[e];
+    bool o = c < 0 || c >= I;
+    if (!o) {
+      const int32_t k = i2ci[c];
+      o = k < 0 || k >= num_ci;
+    }
+    out |= o;
+  }
+  if (__ballot(out)) dead = true;
+  if (dead) {
+    for (int32_t e = tb + lane; e < te; e += 64) pos[e] = -1;
+    if (bad && lane == 0) atomicAdd(bad, 1);
+    return;
+  }
+
+  const float* srow = S + g * num_ci;
+  const uint32_t omv = score_ord(mask_value);
+  if (RANKED) {
+    const int32_t* scr = sc + g * num_ci;
+    const int32_t* prer = pre + g * (num_ci + 1);
+    for (int32_t e = tb + lane; e < te; e += 64) {
+      const int32_t t = tg_col[e];
+      const uint32_t ot = row_has(mask_col, mp0, mp1, t) ? omv : score_ord(srow[i2ci[t]]);
+      int32_t a = 0, z = (int32_t)num_ci;  // the ranked clusters above o_t: places [0, a)
+      while (a < z) {
+        const int32_t mid = (a + z) >> 1;
+        if (score_ord(srow[scr[mid]]) > ot) a = mid + 1; else z = mid;
+      }
+      int acc = prer[a];
+      for (int32_t k = a; k < num_ci; ++k) {  // the tied clusters
+        const int32_t c = scr[k];
+        if (score_ord(srow[c]) != ot) break;
+        int32_t lo, hi;
+        mem_range(mem_ptr, c, I, lo, hi);
+        acc += members_below(mem_item, lo, hi, t);
+      }
+      for (int32_t m = mp0; m < mp1; ++m) {
+        const int32_t mi = mask_col[m];
+        acc += mask_shift(omv, score_ord(srow[i2ci[mi]]), ot, mi, t);
+      }
+      pos[e] = acc;
+    }
+    return;
+  }
+  for (int32_t e = tb; e < te; ++e) {  // wave-uniform
+    const int32_t t = uni(tg_col[e]);
+    const uint32_t ot = row_has(mask_col, mp0, mp1, t) ? omv : score_ord(srow[i2ci[t]]);
+    int acc = 0;
+    for (int64_t c = lane; c < num_ci; c += 64) {
+      const uint32_t oc = score_ord(srow[c]);
+      if (oc < ot) continue;
+      int32_t lo, hi;
+      mem_range(mem_ptr, c, I, lo, hi);
+      acc += oc > ot ? hi - lo : members_below(mem_item, lo, hi, t);
+    }
+    for (int32_t m = mp0 + lane; m < mp1; m += 64) {
+      const int32_t mi = mask_col[m];
+      acc += mask_shift(omv, score_ord(srow[i2ci[mi]]), ot, mi, t);
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) pos[e] = acc;
+  }
+}
+
 // per_user[b] = (precision, recall, ndcg) x nk of user b's list; one wave per user
 constexpr int kMetThreads = 256;
 __global__ __launch_bounds__(kMetThreads) void k_rank_metrics(
@@ -584,6 +1092,87 @@ extern "C" int gdd_rank_metrics(int64_t B, int K, const int32_t* top_item, const
     GDD_LAUNCHED();
   }
   k_rank_metric_sums<<<1, kMetThreads, 0, s>>>(B, 3 * nk, per_user, te_ptr, te_deg, sums, count);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+extern "C" int gdd_score_positions(int64_t B, int64_t I, int d, const int32_t* users, const float* U, int64_t nu,
+                                   const float* V, const int32_t* mask_ptr, const int32_t* mask_col,
+                                   float mask_value, const int32_t* tg_ptr, const int32_t* tg_col, int32_t* pos,
+                                   int32_t* bad, gdd_stream_t stream) {
+  GDD_REQUIRE(B >= 0 && B < INT32_MAX && I >= 1 && I < INT32_MAX && nu >= 1 && nu < INT32_MAX,
+              "score_positions: B=%lld I=%lld nu=%lld unsupported", (long long)B, (long long)I, (long long)nu);
+  GDD_REQUIRE(d >= 1 && d <= kMaxDimTk, "score_positions: d=%d outside [1, %d]", d, kMaxDimTk);
+  if (B == 0) return GDD_OK;
+  GDD_REQUIRE(U && V && tg_ptr, "score_positions: null pointer");
+  GDD_REQUIRE(!mask_ptr || mask_col, "score_positions: mask_ptr without mask_col");
+  const size_t lds = rp_lds(d);
+  const bool vec = (d & 3) == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0;
+  auto kern = !vec       ? k_score_positions<0>
+              : d <= 64  ? k_score_positions<4>
+              : d <= 128 ? k_score_positions<8>
+                         : k_score_positions<16>;
+  if (lds > 65536)
+    GDD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const unsigned grid = (unsigned)((B + kTkUsers - 1) / kTkUsers);
+  kern<<<grid, kTkThreads, lds, to_hip(stream)>>>(B, I, d, users, U, nu, V, mask_ptr, mask_col, mask_value,
+                                                  tg_ptr, tg_col, pos, bad);
+  GDD_LAUNCHED();
+  return GDD_OK;
+}
+
+// workspace: the score of every (user cluster, item cluster), G x num_ci floats; then, where the rows
+// are ranked (num_ci <= kCpSortMax), the ranked cluster ids (G x num_ci) and the prefix sizes
+// (G x (num_ci + 1))
+extern "C" size_t gdd_cluster_positions_ws_bytes(int64_t G, int64_t num_ci) {
+  if (G < 0 || num_ci < 0) return 0;
+  const size_t table = sizeof(float) * (size_t)G * (size_t)num_ci;
+  return num_ci <= kCpSortMax ? 3 * table + sizeof(int32_t) * (size_t)G : table;
+}
+
+extern "C" int gdd_cluster_positions(int64_t B, int64_t I, int64_t num_cu, int64_t num_ci, int d,
+                                     const float* cu_z, const float* ci_z, const int32_t* users, int64_t nu,
+                                     const int32_t* cl_row, int64_t G, const int32_t* groups,
+                                     const int32_t* i2ci, const int32_t* mem_ptr, const int32_t* mem_item,
+                                     const int32_t* mask_ptr, const int32_t* mask_col, float mask_value,
+                                     const int32_t* tg_ptr, const int32_t* tg_col, int32_t* pos, int32_t* bad,
+                                     void* ws, size_t ws_bytes, gdd_stream_t stream) {
+  GDD_REQUIRE(B >= 0 && B < INT32_MAX && I >= 1 && I < INT32_MAX && nu >= 1 && nu < INT32_MAX && G >= 0 &&
+                  G < INT32_MAX && num_cu >= 1 && num_cu < INT32_MAX && num_ci >= 1 && num_ci < INT32_MAX,
+              "cluster_positions: B=%lld I=%lld nu=%lld G=%lld num_cu=%lld num_ci=%lld unsupported", (long long)B,
+              (long long)I, (long long)nu, (long long)G, (long long)num_cu, (long long)num_ci);
+  GDD_REQUIRE(d >= 1 && d <= kMaxDimTk, "cluster_positions: d=%d outside [1, %d]", d, kMaxDimTk);
+  if (B == 0) return GDD_OK;
+  GDD_REQUIRE(cu_z && ci_z && cl_row && groups && i2ci && mem_ptr && mem_item && tg_ptr && G >= 1,
+              "cluster_positions: null pointer");
+  GDD_REQUIRE(!mask_ptr || mask_col, "cluster_positions: mask_ptr without mask_col");
+  GDD_REQUIRE(ws && ws_bytes >= gdd_cluster_positions_ws_bytes(G, num_ci),
+              "cluster_positions: workspace of %zu bytes, %zu needed", ws_bytes,
+              gdd_cluster_positions_ws_bytes(G, num_ci));
+  const int64_t n_ctiles = (num_ci + 63) / 64, n_gtiles = (G + kCsGroups - 1) / kCsGroups;
+  GDD_REQUIRE(n_ctiles * n_gtiles < INT32_MAX, "cluster_positions: G x num_ci too large for one launch");
+  float* S = static_cast<float*>(ws);
+  hipStream_t s = to_hip(stream);
+  k_cluster_scores<<<(unsigned)(n_ctiles * n_gtiles), 256, 0, s>>>(G, num_cu, num_ci, d, n_ctiles, groups, cu_z,
+                                                                   ci_z, S);
+  GDD_LAUNCHED();
+  const unsigned grid = (unsigned)((B + kCxUsers - 1) / kCxUsers);
+  if (num_ci <= kCpSortMax) {
+    int32_t* sc = reinterpret_cast<int32_t*>(S + G * num_ci);
+    int32_t* pre = sc + G * num_ci;
+    int cap = 2;
+    while (cap < num_ci) cap <<= 1;
+    k_cluster_rank_rows<<<(unsigned)G, kCpThreads, sizeof(uint64_t) * cap, s>>>(I, (int)num_ci, cap, S, mem_ptr, sc,
+                                                                                pre);
+    GDD_LAUNCHED();
+    k_cluster_positions<true><<<grid, kCxThreads, 0, s>>>(B, I, num_cu, num_ci, users, nu, cl_row, G, groups, S, sc,
+                                                          pre, i2ci, mem_ptr, mem_item, mask_ptr, mask_col,
+                                                          mask_value, tg_ptr, tg_col, pos, bad);
+  } else {
+    k_cluster_positions<false><<<grid, kCxThreads, 0, s>>>(B, I, num_cu, num_ci, users, nu, cl_row, G, groups, S,
+                                                           nullptr, nullptr, i2ci, mem_ptr, mem_item, mask_ptr,
+                                                           mask_col, mask_value, tg_ptr, tg_col, pos, bad);
+  }
   GDD_LAUNCHED();
   return GDD_OK;
 }

@@ -29,6 +29,9 @@ the reference file:line each entry point replaces):
   from a condensed recommender's cluster tables and maps without expanding them (clusters ranked
   once per user cluster, expanded per user); ``python -m gdd.recommend_distilled`` serves the saved
   artefact
+* :mod:`gdd.rankpos` — :func:`rank_positions` / :func:`rank_positions_condensed`: how many items rank
+  above given items, for every cut-off, MRR and the mean rank (:class:`PositionEvaluator`,
+  :func:`metrics_from_positions`) and for teacher / student :func:`ranking_fidelity`
 * :mod:`gdd.agent` / :mod:`gdd.agent_induct` — the transductive and inductive ClustGDD agents;
   :mod:`gdd.train_clustgdd_transduct` / :mod:`gdd.train_clustgdd_induct` /
   :mod:`gdd.distill_recsys` — the drop-in command lines
@@ -42,6 +45,8 @@ from .graph import (CSRGraph, induced_subgraph, normalize_adj, normalize_adj_ten
                     to_csr)
 from .kmeans import KMeans, MiniBatchKMeans
 from .rankeval import RankingEvaluator, rank_metrics, recommend
+from .rankpos import (PositionEvaluator, fidelity, metrics_from_positions, rank_positions,
+                      rank_positions_condensed, ranking_fidelity)
 from .rankformer import GCNLayer, InteractionGraph, RankformerLayer, RankformerTeacher, save_teacher
 from .sharded import ShardedKMeans, shard_rows
 from .svd import svd_embeddings, truncated_svd
@@ -53,4 +58,6 @@ __all__ = [
     "truncated_svd", "svd_embeddings",
     "InteractionGraph", "RankformerLayer", "GCNLayer", "RankformerTeacher", "save_teacher",
     "recommend", "rank_metrics", "RankingEvaluator", "recommend_condensed", "CondensedRecommender",
+    "rank_positions", "rank_positions_condensed", "metrics_from_positions", "PositionEvaluator", "fidelity",
+    "ranking_fidelity",
 ]

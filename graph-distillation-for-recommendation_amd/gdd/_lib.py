@@ -179,6 +179,12 @@ SIGNATURES = {
     "gdd_cluster_expand_topk": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp, _c_i64, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _c_f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gdd_rank_metrics": (_c_int, [_c_i64, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gdd_score_positions": (_c_int, [_c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_f32, _vp, _vp,
+                                     _vp, _vp, _vp]),
+    "gdd_cluster_positions_ws_bytes": (_c_size, [_c_i64, _c_i64]),
+    "gdd_cluster_positions": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _c_i64, _vp, _c_i64,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _c_f32, _vp, _vp, _vp, _vp, _vp, _c_size,
+                                       _vp]),
     "gdd_infonce_ws_bytes": (_c_size, [_c_i64, _c_int]),
     "gdd_infonce_rows": (_c_int, [_c_i64, _c_int, _vp, _vp, _c_f32, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
     "gdd_infonce_cols": (_c_int, [_c_i64, _c_int, _vp, _vp, _c_f32, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),

@@ -255,6 +255,14 @@ class CondensedRecommender:
         items, scores = self._lists(k, ids, mask_np, mask_value, return_scores)
         return (items, scores) if return_scores else items
 
+    def positions(self, targets, users=None, exclude=None, mask_value: float = -1024.0) -> torch.Tensor:
+        """As :func:`gdd.rankpos.rank_positions` on ``(cu_z[u2cu], ci_z[i2ci])``: the number of items
+        ranked above each target, int32 on the device, from the cluster tables
+        (``gdd_cluster_positions``). ``last_info`` then holds ``ranked_clusters`` and
+        ``workspace_bytes``."""
+        from .rankpos import condensed_positions
+        return condensed_positions(self, targets, users, exclude, mask_value)
+
 
 def recommend_condensed(cu_z: torch.Tensor, ci_z: torch.Tensor, u2cu, i2ci, k: int, users=None, exclude=None,
                         mask_value: float = -1024.0, return_scores: bool = False):

@@ -27,6 +27,12 @@ embeddings. With ``--report_from_clusters`` the condensed model's lines are comp
 tables (:mod:`gdd.condrank`) without expanding them; the lines are the same. The saved artefact is
 served by :mod:`gdd.recommend_distilled`.
 
+``--report_full_ranking`` prints the same three metrics from full-ranking positions
+(:class:`gdd.rankpos.PositionEvaluator`), so ``--report_topks`` may exceed 256 for it, then MRR and the
+mean rank of the held-out items; ``--report_fidelity`` (with ``--teacher_path``) prints how much of the
+teacher's top-k lists the condensed model keeps (:func:`gdd.rankpos.ranking_fidelity`, the cut-offs up
+to 256). Both go through ``gdd_cluster_positions`` with ``--report_from_clusters``.
+
 The reference falls back to the CPU when no GPU is visible; this driver has no CPU path.
 """
 from __future__ import annotations
@@ -147,6 +153,13 @@ def parse_args(argv=None):
     p.add_argument("--report_from_clusters", action="store_true",
                    help="with --report_ranking: rank the condensed model from its cluster tables "
                         "(gdd.condrank) instead of expanding them to every user and item; the same lines")
+    p.add_argument("--report_full_ranking", action="store_true",
+                   help="after refinement print NDCG / recall / precision at --report_topks (any cut-offs up to "
+                        "the number of items), MRR and the mean rank of the held-out items of the refined "
+                        "condensed model, from full-ranking positions (gdd.rankpos)")
+    p.add_argument("--report_fidelity", action="store_true",
+                   help="with --teacher_path: print how much of the teacher's top-k lists (the cut-offs of "
+                        "--report_topks up to 256) the refined condensed model keeps")
     return p.parse_args(argv)
 
 
@@ -159,6 +172,8 @@ def run(args, out_root: str = "ClustGDD", embeddings=None, timings: Optional[dic
     np.random.seed(args.seed)
     if not torch.cuda.is_available():
         raise RuntimeError("gdd.distill_recsys: no HIP device visible (the MI355X path has no CPU fallback)")
+    if getattr(args, "report_fidelity", False) and args.teacher_path is None:
+        raise ValueError("--report_fidelity needs --teacher_path")
     device = torch.device(args.device if args.device.startswith("cuda") else "cuda")
     print(f"[env] device={device}")
 
@@ -283,6 +298,36 @@ def run(args, out_root: str = "ClustGDD", embeddings=None, timings: Optional[dic
             m = ranking(tu, ti)
             for line in format_metrics(topks, m):
                 print(f"[rank] teacher ({m['users']} users): {line}")
+
+    full, fid = getattr(args, "report_full_ranking", False), getattr(args, "report_fidelity", False)
+    if full or fid:
+        from .condrank import CondensedRecommender
+        from .rankeval import MAX_K
+        from .rankpos import (PositionEvaluator, format_fidelity, format_full_metrics, parse_cutoffs,
+                              ranking_fidelity)
+        topks = parse_cutoffs(args.report_topks if getattr(args, "report_topks", None) else int(args.eval_topk),
+                              ds.num_items)
+        fid_topks = tuple(k for k in topks if k <= MAX_K)  # the teacher's lists are recommend()'s
+        if fid and not fid_topks:
+            raise ValueError(f"--report_fidelity needs a cut-off of --report_topks at or below {MAX_K}")
+        positions = PositionEvaluator(R_train, ds.test_u, ds.test_i, topks, device, mask_value=-1e9,
+                                      max_users=args.eval_max_users)
+        from_clusters = getattr(args, "report_from_clusters", False)
+        model.eval()
+        with torch.no_grad():
+            cu_z, ci_z = model.propagate()
+            if full:
+                m = (positions.condensed(cu_z, ci_z, u2cu, i2ci) if from_clusters
+                     else positions(cu_z[u2cu_t], ci_z[i2ci_t]))
+                for line in format_full_metrics(topks, m):
+                    print(f"[rank-full] condensed ({m['users']} users): {line}")
+            if fid:
+                student = (CondensedRecommender(cu_z, ci_z, u2cu, i2ci) if from_clusters
+                           else (cu_z[u2cu_t], ci_z[i2ci_t]))
+                f = ranking_fidelity((tu, ti), student, fid_topks, users=positions.users, exclude=R_train,
+                                     mask_value=-1e9)
+                for line in format_fidelity(fid_topks, f):
+                    print(f"[fidelity] {line}")
 
     out_dir = os.path.join(out_root, "distilled_recsys", args.dataset)
     R.save_distilled(out_dir, model, u2cu, i2ci, num_cu, num_ci)

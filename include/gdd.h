@@ -769,6 +769,50 @@ int gdd_rank_metrics(int64_t B, int K, const int32_t* top_item, const int32_t* t
                      double* per_user, double* sums, int64_t* count, gdd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* Full-ranking positions (Rankformer/code/model.py:252-343 evaluate, :27-53 test, for metrics past  */
+/* a list of 256: any cut-off, MRR, mean rank, fidelity; DESIGN.md "Full-ranking positions").        */
+/* With key(b, i) the u64 order of gdd_score_topk (score chain or mask_value, then item id):         */
+/*   pos(b, t) = #{ i in [0, I) : key(b, i) > key(b, t) },                                           */
+/* the index at which gdd_score_topk with K = I would list t. Targets are a CSR of B rows in the     */
+/* order of the call (tg_ptr [B + 1], tg_col, int32): any order, repeats allowed, rows of any length */
+/* (0 included), a masked target carries mask_value. pos (int32, one per entry of tg_col, same       */
+/* order). A user id outside [0, nu), a mask column or a target column outside [0, I) is not         */
+/* dereferenced: every position of that row is -1 and *bad (device int, nullable, not cleared here)  */
+/* is incremented once. No B x I buffer, integer atomics only: two runs give the same integers.      */
+/* gdd_score_positions (model.py:252-343, :27-53): users, U, nu, V, mask_ptr / mask_col (columns     */
+/*   ascending), mask_value and the limits on B, I, d as in gdd_score_topk. No workspace. A          */
+/*   workgroup of 16 users passes over V once per 256 targets of its longest row.                    */
+/* gdd_cluster_positions_ws_bytes (model.py:252-343, :27-53): the workspace of                       */
+/*   gdd_cluster_positions: the score of every (user cluster, item cluster) pair, 4 G num_ci bytes,  */
+/*   and for num_ci <= 4096 each user cluster's row in ranked order with the prefix sums of the      */
+/*   cluster sizes, 4 G (2 num_ci + 1) bytes more.                                                   */
+/* gdd_cluster_positions (model.py:252-343, :27-53 for a condensed model): the same integers for     */
+/*   U[b] = cu_z[u2cu[b]], V[i] = ci_z[i2ci[i]] without either table. cu_z (num_cu x d), ci_z        */
+/*   (num_ci x d); groups [G] the distinct user clusters of the call, cl_row[b] in [0, G) the entry  */
+/*   of groups that is user b's cluster; users (nullable) for the range check alone; i2ci [I] the    */
+/*   cluster of every item (device); mem_ptr / mem_item as in gdd_cluster_expand_topk; the mask      */
+/*   columns of a row strictly ascending. With o(.) the high word of the key, o_t = o(mask_value) if */
+/*   t is masked, else o(S[i2ci[t]]), S the chain scores of the user's cluster:                      */
+/*     pos = sum over clusters c of [o(S[c]) > o_t] size_c + [o(S[c]) == o_t] #{members below t}     */
+/*         + sum over masked m of [mask_value ranks m above t] - [S[i2ci[m]] ranks m above t].       */
+/*   With ranked rows (num_ci <= 4096) the first sum is one binary search and one prefix entry per   */
+/*   target and only tied clusters and the mask row are walked; else every cluster is visited.       */
+/*   Besides the cases above, a cl_row outside [0, G), a group outside [0, num_cu) or an i2ci of a   */
+/*   mask or target column outside [0, num_ci) gives the -1 row. mem_ptr is clamped to [0, I].       */
+/* ---------------------------------------------------------------------------------------------- */
+int gdd_score_positions(int64_t B, int64_t I, int d, const int32_t* users, const float* U, int64_t nu,
+                        const float* V, const int32_t* mask_ptr, const int32_t* mask_col, float mask_value,
+                        const int32_t* tg_ptr, const int32_t* tg_col, int32_t* pos, int32_t* bad,
+                        gdd_stream_t stream);
+size_t gdd_cluster_positions_ws_bytes(int64_t G, int64_t num_ci);
+int gdd_cluster_positions(int64_t B, int64_t I, int64_t num_cu, int64_t num_ci, int d, const float* cu_z,
+                          const float* ci_z, const int32_t* users, int64_t nu, const int32_t* cl_row, int64_t G,
+                          const int32_t* groups, const int32_t* i2ci, const int32_t* mem_ptr,
+                          const int32_t* mem_item, const int32_t* mask_ptr, const int32_t* mask_col,
+                          float mask_value, const int32_t* tg_ptr, const int32_t* tg_col, int32_t* pos,
+                          int32_t* bad, void* ws, size_t ws_bytes, gdd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* The teacher's contrastive loss (Rankformer/code/model.py:10-24 InfoNCE, :449-465 its use in the   */
 /* loss; DESIGN.md "Contrastive loss"). A, Y: B x d fp32 row-major (the caller normalises; unit rows */
 /* are not assumed), 1 <= d <= gdd_rank_max_dim(), 0 <= B < 2^31 (B == 0 returns without a launch),  */
