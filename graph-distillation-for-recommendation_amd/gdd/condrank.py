@@ -28,7 +28,8 @@ import scipy.sparse as sp
 import torch
 
 from . import _lib
-from .rankeval import MAX_K, _check_k, _check_tables, _f32, _np_ids, _raise_bad, _rows_of, _score_topk
+from .rankeval import (MAX_K, _check_k, _check_tables, _check_users, _f32, _gather_rows, _np_ids, _raise_bad,
+                       _rows_of, _score_topk, _to_dev)
 
 MAX_LIST = MAX_K  # clusters ranked per user cluster: one gdd_score_topk list
 
@@ -91,16 +92,8 @@ def mask_rows(exclude, ids: Optional[np.ndarray], num_users: int, num_items: int
                 raise ValueError("exclude has no row for some selected user")
             ptr = m.indptr[:num_users + 1]
             return ptr.astype(np.int32), m.indices[:ptr[-1]].astype(np.int32)
-        if ids.size and (ids.min() < 0 or ids.max() >= n_rows):
-            raise ValueError("exclude has no row for some selected user")
-        ptr = m.indptr.astype(np.int64)
-        lens = ptr[ids + 1] - ptr[ids]
-        out = np.zeros(ids.shape[0] + 1, np.int64)
-        np.cumsum(lens, out=out[1:])
-        if out[-1] >= 2 ** 31:
-            raise ValueError("exclude rows outside int32")
-        gather = np.repeat(ptr[ids] - out[:-1], lens) + np.arange(out[-1])
-        return out.astype(np.int32), m.indices[gather].astype(np.int32)
+        ptr, col = _gather_rows(m.indptr, m.indices, ids)
+        return ptr, col.astype(np.int32)
     return _distinct_columns(*_rows_of(exclude, ids if ids is not None else np.arange(num_users), num_items))
 
 
@@ -159,12 +152,19 @@ class CondensedRecommender:
     def _prepare(self):
         if self._dev is None:
             _lib.device_lib()
-            dev = self.device
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            t = lambda a, dt=None: _to_dev(a, self.device, dt)  # noqa: E731
             mp, mi = self._mem_host
             self._dev = dict(cu_z=_f32(self._tables[0]), ci_z=_f32(self._tables[1]), mem_ptr=t(mp), mem_item=t(mi),
-                             u2cu=t(self._u2cu.astype(np.int32)), i2ci=t(self._i2ci))
+                             u2cu=t(self._u2cu, np.int32), i2ci=t(self._i2ci))
         return self._dev
+
+    def _grouped(self, ids: Optional[np.ndarray]):
+        """The user clusters of a request (``ids``: checked user ids or None, every user), at least one
+        user: ``(cl_of, groups_t, row_t)``, the cluster of each user on the host, the distinct clusters
+        and each user's index into them as int32 device tensors (``G = groups_t.numel()``)."""
+        cl_of = self._u2cu if ids is None else self._u2cu[ids]
+        groups, row = np.unique(cl_of, return_inverse=True)
+        return cl_of, _to_dev(groups, self.device, np.int32), _to_dev(row.ravel(), self.device, np.int32)
 
     @property
     def cu_z(self) -> torch.Tensor:
@@ -194,22 +194,20 @@ class CondensedRecommender:
         int32 host CSR with strictly ascending columns (:func:`mask_rows`) or None."""
         g = self._prepare()
         dev = self.device
-        cl_of = self._u2cu if ids is None else self._u2cu[ids]
-        B = int(cl_of.shape[0])
+        B = self.num_users if ids is None else int(ids.shape[0])
         L = min(self.num_ci, MAX_LIST)
         items = torch.empty(B, k, dtype=torch.int32, device=dev)
         scores = torch.empty(B, k, dtype=torch.float32, device=dev) if return_scores else None
         if B == 0:
             self.last_info = {"fallback_users": 0, "ranked_clusters": 0, "list_len": L}
             return items, scores
-        groups, row = np.unique(cl_of, return_inverse=True)
-        G = int(groups.shape[0])
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
-        groups_t, row_t = t(groups, np.int32), t(row.ravel(), np.int32)
-        users_t = None if ids is None else t(ids, np.int32)
+        cl_of, groups_t, row_t = self._grouped(ids)
+        G = int(groups_t.numel())
+        t = lambda a: _to_dev(a, dev, np.int32)  # noqa: E731
+        users_t = None if ids is None else t(ids)
         mask = None
         if mask_np is not None and int(mask_np[1].shape[0]):
-            mask = (t(mask_np[0], np.int32), t(mask_np[1], np.int32))
+            mask = (t(mask_np[0]), t(mask_np[1]))
         counters = torch.zeros(2, dtype=torch.int32, device=dev)  # bad rows, incomplete rows
         cl_item, cl_score = _score_topk(g["cu_z"], g["ci_z"], L, groups_t, None, 0.0, True, counters[:1])
         incomplete = torch.empty(B, dtype=torch.int32, device=dev)
@@ -228,9 +226,9 @@ class CondensedRecommender:
             sel_np = sel.cpu().numpy()
             fb_mask = None
             if mask is not None:
-                fb_mask = tuple(t(a, np.int32) for a in _rows_of(mask_np, sel_np, self.num_items))
-            fb_items, fb_scores = _score_topk(g["cu_z"], self.expanded_items(), k, t(cl_of[sel_np], np.int32),
-                                              fb_mask, mask_value, return_scores, counters[:1])
+                fb_mask = tuple(t(a) for a in _rows_of(mask_np, sel_np, self.num_items))
+            fb_items, fb_scores = _score_topk(g["cu_z"], self.expanded_items(), k, t(cl_of[sel_np]), fb_mask,
+                                              mask_value, return_scores, counters[:1])
             items[sel] = fb_items
             if return_scores:
                 scores[sel] = fb_scores
@@ -244,11 +242,7 @@ class CondensedRecommender:
         user ids (default: every user, in order; repeats allowed), ``exclude`` a scipy sparse matrix
         or ``(ptr, col)`` CSR over the original users and items."""
         k = _check_k(k, self.num_items)
-        ids = None
-        if users is not None:
-            ids = _np_ids(users)
-            if ids.size and (ids.min() < 0 or ids.max() >= self.num_users):
-                raise ValueError(f"users holds an id outside [0, {self.num_users})")
+        ids = _check_users(users, self.num_users)
         mask_np = None
         if exclude is not None:
             mask_np = mask_rows(exclude, ids, self.num_users, self.num_items)

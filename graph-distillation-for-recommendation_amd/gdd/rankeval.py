@@ -30,16 +30,21 @@ MAX_DIM = 256  # gdd_rank_max_dim()
 MAX_TOPKS = 8  # gdd_rank_metrics: one lane per cut-off
 
 
-def parse_topks(text) -> Tuple[int, ...]:
-    """``--topks "[20, 50]"`` as a tuple of ints (``ast.literal_eval``; the reference uses ``eval``,
-    parse.py:85)."""
+def _parse_int_list(text) -> list:
+    """``"[20, 50]"``, ``"20"`` or the value itself as a list or tuple of integers
+    (``ast.literal_eval``; the reference uses ``eval``, parse.py:85)."""
     v = ast.literal_eval(text) if isinstance(text, str) else text
     if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
         v = [v]
     if not isinstance(v, (list, tuple)) or any(isinstance(k, bool) or not isinstance(k, (int, np.integer))
                                                 for k in v):
         raise ValueError(f"topks must be a list of integers, got {text!r}")
-    return check_topks(v)
+    return v
+
+
+def parse_topks(text) -> Tuple[int, ...]:
+    """``--topks "[20, 50]"`` as a tuple of ints."""
+    return check_topks(_parse_int_list(text))
 
 
 def check_topks(topks, num_items: Optional[int] = None) -> Tuple[int, ...]:
@@ -79,16 +84,20 @@ def _np_ids(a) -> np.ndarray:
     return np.asarray(a, dtype=np.int64).ravel()
 
 
-def _rows_of(exclude, users: np.ndarray, num_items: int) -> Tuple[np.ndarray, np.ndarray]:
-    """The rows ``users`` of ``exclude`` (scipy sparse, or ``(ptr, col)`` over all users) as an int32
-    CSR in the order of ``users``, columns ascending."""
-    if sp.issparse(exclude):
-        m = sp.csr_matrix(exclude)
-        ptr, col = np.asarray(m.indptr, np.int64), np.asarray(m.indices, np.int64)
-    else:
-        ptr, col = (_np_ids(x) for x in exclude)
-    n_rows = ptr.shape[0] - 1
-    if users.size and (users.min() < 0 or users.max() >= n_rows):
+def _check_users(users, num_users: int) -> Optional[np.ndarray]:
+    if users is None:
+        return None
+    ids = _np_ids(users)
+    if ids.size and (ids.min() < 0 or ids.max() >= num_users):
+        raise ValueError(f"users holds an id outside [0, {num_users})")
+    return ids
+
+
+def _gather_rows(ptr: np.ndarray, col: np.ndarray, users: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The rows ``users`` of the CSR ``(ptr, col)`` in that order, columns as stored: ``(int32 ptr,
+    col)``."""
+    ptr = np.asarray(ptr, np.int64)
+    if users.size and (users.min() < 0 or users.max() >= ptr.shape[0] - 1):
         raise ValueError("exclude has no row for some selected user")
     lens = ptr[users + 1] - ptr[users]
     out_ptr = np.zeros(users.shape[0] + 1, np.int64)
@@ -96,14 +105,32 @@ def _rows_of(exclude, users: np.ndarray, num_items: int) -> Tuple[np.ndarray, np
     if out_ptr[-1] >= 2 ** 31:
         raise ValueError("exclude rows outside int32")
     gather = np.repeat(ptr[users] - out_ptr[:-1], lens) + np.arange(out_ptr[-1])
-    c = col[gather]
-    row = np.repeat(np.arange(users.shape[0]), lens)
+    return out_ptr.astype(np.int32), col[gather]
+
+
+def _rows_of(exclude, users: np.ndarray, num_items: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The rows ``users`` of ``exclude`` (scipy sparse, or ``(ptr, col)`` over all users) as an int32
+    CSR in the order of ``users``, columns ascending."""
+    if sp.issparse(exclude):
+        m = sp.csr_matrix(exclude)
+        ptr, col = m.indptr, np.asarray(m.indices, np.int64)
+    else:
+        ptr, col = (_np_ids(x) for x in exclude)
+    out_ptr, c = _gather_rows(ptr, col, users)
+    row = np.repeat(np.arange(users.shape[0]), np.diff(out_ptr))
     c = c[np.lexsort((c, row))]  # rows stay in place, each sorted by column
-    return out_ptr.astype(np.int32), c.astype(np.int32)
+    return out_ptr, c.astype(np.int32)
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
+
+
+def _to_dev(a, dev, dtype=None) -> torch.Tensor:
+    """A host array (as ``dtype``, if given) or a tensor on ``dev``."""
+    if isinstance(a, torch.Tensor):
+        return a.to(dev)
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
 
 
 def _score_topk(user_emb, item_emb, k, users_t, mask, mask_value, return_scores, bad):
@@ -137,19 +164,15 @@ def recommend(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int, users=None
     in ascending order; equal scores rank in ascending item id."""
     nu, ni, _ = _check_tables(user_emb, item_emb)
     k = _check_k(k, ni)
-    ids = None
-    if users is not None:
-        ids = _np_ids(users)
-        if ids.size and (ids.min() < 0 or ids.max() >= nu):
-            raise ValueError(f"users holds an id outside [0, {nu})")
+    ids = _check_users(users, nu)
     mask_np = None
     if exclude is not None:
         # item ids are checked by the kernel (a row with one outside [0, I) comes back as -1)
         mask_np = _rows_of(exclude, ids if ids is not None else np.arange(nu), ni)
     dev = item_emb.device
     _lib.device_lib()
-    users_t = None if ids is None else torch.from_numpy(ids.astype(np.int32)).to(dev)
-    mask = None if mask_np is None else tuple(torch.from_numpy(a).to(dev) for a in mask_np)
+    users_t = None if ids is None else _to_dev(ids, dev, np.int32)
+    mask = None if mask_np is None else tuple(_to_dev(a, dev) for a in mask_np)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     items, scores = _score_topk(user_emb, item_emb, k, users_t, mask, mask_value, return_scores, bad)
     n_bad = int(bad.item())
@@ -239,19 +262,42 @@ class RankingEvaluator:
             _lib.device_lib()
             dev = self.device
             (mp, mc), te_ptr, te_col, deg = self._host
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            t = lambda a, dt=None: _to_dev(a, dev, dt)  # noqa: E731
             nk = len(self.topks)
-            self._dev = dict(users=t(self.users.astype(np.int32)), mask=(t(mp), t(mc)), te_ptr=t(te_ptr),
-                             te_col=t(te_col), deg=t(deg), tk=t(np.asarray(self.topks, np.int32)),
+            self._dev = dict(users=t(self.users, np.int32), mask=(t(mp), t(mc)), te_ptr=t(te_ptr),
+                             te_col=t(te_col), deg=t(deg), tk=t(self.topks, np.int32),
                              inv=t(1.0 / np.log2(np.arange(self.k, dtype=np.float64) + 2.0)),
                              out=torch.zeros(3 * nk + 2, dtype=torch.float64, device=dev))
         return self._dev
 
+    def _check_size(self, num_users: int, num_items: int, what: str) -> None:
+        if num_users != self.num_users or num_items != self.num_items:
+            raise ValueError(f"{what} of {num_users} users x {num_items} items for an evaluator of "
+                             f"{self.num_users} x {self.num_items}")
+
+    def _empty(self, nk: Optional[int] = None) -> dict:
+        """The result over no users (``nk`` cut-offs, default: this evaluator's)."""
+        z = np.zeros(len(self.topks) if nk is None else nk)
+        return {"precision": z.copy(), "recall": z.copy(), "ndcg": z.copy(), "users": 0}
+
+    def _metrics(self, items: torch.Tensor) -> torch.Tensor:
+        """``gdd_rank_metrics`` on the evaluated users' lists; the host copy of ``out``: sums, count and
+        the bad-row counter in one copy."""
+        g = self._dev
+        _rank_metrics(_lib.device_lib(), items, g["te_ptr"], g["te_col"], g["deg"], g["tk"], g["inv"],
+                      len(self.topks), g["out"])
+        return g["out"].cpu()
+
+    def _means(self, host: torch.Tensor) -> dict:
+        nk = len(self.topks)
+        count = int(host[3 * nk:3 * nk + 1].view(torch.int64)[0])
+        means = host[:3 * nk].view(3, nk).numpy() / max(count, 1)
+        return {"precision": means[0].copy(), "recall": means[1].copy(), "ndcg": means[2].copy(),
+                "users": count}
+
     def _lists(self, user_emb, item_emb, return_scores=False):
         nu, ni, _ = _check_tables(user_emb, item_emb)
-        if nu != self.num_users or ni != self.num_items:
-            raise ValueError(f"embeddings of {nu} users x {ni} items for an evaluator of "
-                             f"{self.num_users} x {self.num_items}")
+        self._check_size(nu, ni, "embeddings")
         g = self._prepare()
         bad = g["out"][-1:].view(torch.int32)[:1]
         return _score_topk(user_emb, item_emb, self.k, g["users"], g["mask"], self.mask_value, return_scores,
@@ -269,23 +315,15 @@ class RankingEvaluator:
 
     @torch.no_grad()
     def __call__(self, user_emb: torch.Tensor, item_emb: torch.Tensor) -> dict:
-        nk = len(self.topks)
         if self.users.size == 0:
-            z = np.zeros(nk)
-            return {"precision": z.copy(), "recall": z.copy(), "ndcg": z.copy(), "users": 0}
+            return self._empty()
         items, _ = self._lists(user_emb, item_emb)
-        g = self._dev
-        _rank_metrics(_lib.device_lib(), items, g["te_ptr"], g["te_col"], g["deg"], g["tk"], g["inv"], nk,
-                      g["out"])
-        host = g["out"].cpu()  # sums, count and the bad-row counter in one copy
+        host = self._metrics(items)
         n_bad = int(host[-1:].view(torch.int32)[0])
         if n_bad:
-            g["out"][-1:].zero_()
+            self._dev["out"][-1:].zero_()
             _raise_bad(n_bad)
-        count = int(host[3 * nk:3 * nk + 1].view(torch.int64)[0])
-        means = host[:3 * nk].view(3, nk).numpy() / max(count, 1)
-        return {"precision": means[0].copy(), "recall": means[1].copy(), "ndcg": means[2].copy(),
-                "users": count}
+        return self._means(host)
 
     @torch.no_grad()
     def condensed(self, cu_z: torch.Tensor, ci_z: torch.Tensor, u2cu, i2ci) -> dict:
@@ -293,23 +331,13 @@ class RankingEvaluator:
         :class:`gdd.condrank.CondensedRecommender` (the same items, so the same metrics) and
         ``gdd_rank_metrics``."""
         from .condrank import CondensedRecommender, _distinct_columns
-        rec =CondensedRecommender(cu_z, ci_z, u2cu, i2ci)
-        if rec.num_users != self.num_users or rec.num_items != self.num_items:
-            raise ValueError(f"cluster maps of {rec.num_users} users x {rec.num_items} items for an evaluator "
-                             f"of {self.num_users} x {self.num_items}")
-        nk = len(self.topks)
+        rec = CondensedRecommender(cu_z, ci_z, u2cu, i2ci)
+        self._check_size(rec.num_users, rec.num_items, "cluster maps")
         if self.users.size == 0:
-            z = np.zeros(nk)
-            return {"precision": z.copy(), "recall": z.copy(), "ndcg": z.copy(), "users": 0}
-        g = self._prepare()
+            return self._empty()
+        self._prepare()
         items, _ = rec._lists(self.k, self.users, _distinct_columns(*self._host[0]), self.mask_value, False)
-        _rank_metrics(_lib.device_lib(), items, g["te_ptr"], g["te_col"], g["deg"], g["tk"], g["inv"], nk,
-                      g["out"])
-        host = g["out"].cpu()
-        count = int(host[3 * nk:3 * nk + 1].view(torch.int64)[0])
-        means = host[:3 * nk].view(3, nk).numpy() / max(count, 1)
-        return {"precision": means[0].copy(), "recall": means[1].copy(), "ndcg": means[2].copy(),
-                "users": count}
+        return self._means(self._metrics(items))  # rec._lists has its own bad-row counter
 
 
 def format_metrics(topks: Sequence[int], m: dict) -> list:

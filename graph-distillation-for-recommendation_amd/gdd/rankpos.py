@@ -22,7 +22,6 @@ is touched. There is no CPU path.
 """
 from __future__ import annotations
 
-import ast
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -30,7 +29,8 @@ import scipy.sparse as sp
 import torch
 
 from . import _lib
-from .rankeval import RankingEvaluator, _check_tables, _f32, _np_ids, _rows_of, recommend
+from .rankeval import (RankingEvaluator, _check_tables, _check_users, _f32, _np_ids, _parse_int_list, _rows_of,
+                       _to_dev, recommend)
 
 _BLOCK_ELEMS = 1 << 22  # metrics_from_positions: padded doubles per block of users
 
@@ -53,27 +53,12 @@ def check_cutoffs(topks, num_items: Optional[int] = None) -> Tuple[int, ...]:
 def parse_cutoffs(text, num_items: Optional[int] = None) -> Tuple[int, ...]:
     """``--report_topks "[20, 500]"`` as a tuple of ints (``ast.literal_eval``), without the limits of
     :func:`gdd.rankeval.parse_topks`."""
-    v = ast.literal_eval(text) if isinstance(text, str) else text
-    if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
-        v = [v]
-    if not isinstance(v, (list, tuple)) or any(isinstance(k, bool) or not isinstance(k, (int, np.integer))
-                                                for k in v):
-        raise ValueError(f"topks must be a list of integers, got {text!r}")
-    return check_cutoffs(v, num_items)
+    return check_cutoffs(_parse_int_list(text), num_items)
 
 
 def _raise_bad(n: int) -> None:
     raise RuntimeError(f"rank positions: {n} row(s) with a user id, an excluded item id or a target item id out "
                        "of range (those rows are -1)")
-
-
-def _check_users(users, num_users: int) -> Optional[np.ndarray]:
-    if users is None:
-        return None
-    ids = _np_ids(users)
-    if ids.size and (ids.min() < 0 or ids.max() >= num_users):
-        raise ValueError(f"users holds an id outside [0, {num_users})")
-    return ids
 
 
 def _check_targets(targets, batch: int, num_items: int):
@@ -117,12 +102,6 @@ def _check_targets(targets, batch: int, num_items: int):
     return ptr, np.ascontiguousarray(a, dtype=np.int32).ravel(), width
 
 
-def _to_dev(a, dev) -> torch.Tensor:
-    if isinstance(a, torch.Tensor):
-        return a.to(dev)
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
 def _score_positions(user_emb, item_emb, users_t, mask, mask_value, tg_ptr, tg_col, bad) -> torch.Tensor:
     """One ``gdd_score_positions`` launch on prepared int32 device tensors (``users_t`` / ``mask`` may
     be None)."""
@@ -154,7 +133,7 @@ def rank_positions(user_emb: torch.Tensor, item_emb: torch.Tensor, targets, user
     mask_np = None if exclude is None else _rows_of(exclude, ids if ids is not None else np.arange(nu), ni)
     dev = item_emb.device
     _lib.device_lib()
-    users_t = None if ids is None else _to_dev(ids.astype(np.int32), dev)
+    users_t = None if ids is None else _to_dev(ids, dev, np.int32)
     mask = None if mask_np is None else tuple(_to_dev(a, dev) for a in mask_np)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     pos = _score_positions(user_emb, item_emb, users_t, mask, mask_value, _to_dev(ptr, dev), _to_dev(col, dev),
@@ -177,19 +156,16 @@ def _cluster_positions(rec, ids: Optional[np.ndarray], mask_np, mask_value: floa
     ``tg_col``: int32; each as host arrays or device tensors."""
     g = rec._prepare()
     dev = rec.device
-    cl_of = rec._u2cu if ids is None else rec._u2cu[ids]
-    B = int(cl_of.shape[0])
+    B = rec.num_users if ids is None else int(ids.shape[0])
     tg_ptr, tg_col = _to_dev(tg_ptr, dev), _to_dev(tg_col, dev)
     pos = torch.empty(int(tg_col.numel()), dtype=torch.int32, device=dev)
     if B == 0:
         return pos
     if "i2ci32" not in g:
         g["i2ci32"] = g["i2ci"].to(torch.int32)
-    groups, row = np.unique(cl_of, return_inverse=True)
-    G = int(groups.shape[0])
-    users_t = None if ids is None else _to_dev(ids.astype(np.int32), dev)
-    # named, so that they live until the launch is enqueued
-    row_t, groups_t = _to_dev(row.ravel().astype(np.int32), dev), _to_dev(groups.astype(np.int32), dev)
+    _, groups_t, row_t = rec._grouped(ids)  # named, so that they live until the launch is enqueued
+    G = int(groups_t.numel())
+    users_t = None if ids is None else _to_dev(ids, dev, np.int32)
     mp = mc = None
     if mask_np is not None and int(mask_np[1].shape[0]):
         mp, mc = (_to_dev(a, dev) for a in mask_np)
@@ -327,17 +303,13 @@ class PositionEvaluator:
         return {k: m[k] for k in ("precision", "recall", "ndcg", "mrr", "mean_rank", "users")}
 
     def _empty(self) -> dict:
-        z = np.zeros(len(self.topks))
-        return {"precision": z.copy(), "recall": z.copy(), "ndcg": z.copy(), "mrr": 0.0, "mean_rank": 0.0,
-                "users": 0}
+        return {**self._prep._empty(len(self.topks)), "mrr": 0.0, "mean_rank": 0.0}
 
     @torch.no_grad()
     def positions(self, user_emb: torch.Tensor, item_emb: torch.Tensor) -> torch.Tensor:
         """The positions of the evaluated users' distinct held-out items (CSR order of the split)."""
         nu, ni, _ = _check_tables(user_emb, item_emb)
-        if nu != self.num_users or ni != self.num_items:
-            raise ValueError(f"embeddings of {nu} users x {ni} items for an evaluator of "
-                             f"{self.num_users} x {self.num_items}")
+        self._prep._check_size(nu, ni, "embeddings")
         g = self._prep._prepare()
         bad = torch.zeros(1, dtype=torch.int32, device=self.device)
         pos = _score_positions(user_emb, item_emb, g["users"], g["mask"], self.mask_value, g["te_ptr"],
@@ -360,9 +332,7 @@ class PositionEvaluator:
         (``gdd_cluster_positions``: the same positions, so the same numbers)."""
         from .condrank import CondensedRecommender, _distinct_columns
         rec = CondensedRecommender(cu_z, ci_z, u2cu, i2ci)
-        if rec.num_users != self.num_users or rec.num_items != self.num_items:
-            raise ValueError(f"cluster maps of {rec.num_users} users x {rec.num_items} items for an evaluator "
-                             f"of {self.num_users} x {self.num_items}")
+        self._prep._check_size(rec.num_users, rec.num_items, "cluster maps")
         if self.users.size == 0:
             return self._empty()
         g = self._prep._prepare()

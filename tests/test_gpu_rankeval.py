@@ -45,9 +45,19 @@ def random_mask(rng, nu, I, frac=0.05):
     return R.csr_of(r, c, nu)
 
 
-def device_lists(U, V, k, users=None, mask=None, mask_value=-1024.0):
+def dev_off4(a):
+    """``a`` on the device, contiguous, its first element 4 bytes past a 16-byte boundary."""
+    flat = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
+    t = flat[1:1 + a.size].view(*a.shape)
+    t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    assert t.is_contiguous() and t.data_ptr() % 16 == 4
+    return t
+
+
+def device_lists(U, V, k, users=None, mask=None, mask_value=-1024.0, vdev=dev):
     import gdd
-    items, scores = gdd.recommend(dev(U), dev(V), k, users=users, exclude=mask, mask_value=mask_value,
+    Vt = vdev(V)
+    items, scores = gdd.recommend(dev(U), Vt, k, users=users, exclude=mask, mask_value=mask_value,
                                   return_scores=True)
     assert items.dtype == torch.int32 and scores.dtype == torch.float32 and items.is_cuda
     return items.cpu().numpy(), scores.cpu().numpy()
@@ -59,14 +69,27 @@ def reference_lists(U, V, k, users=None, mask=None, mask_value=-1024.0):
     return R.ranked(R.scores64(U, V, sel, m, mask_value), k)
 
 
-# (I, K, d, B): every I, K, d and B of the issue's cross at least once; K = I where I <= 256
+# (I, K, d, B): every I, K, d and B of the issue's cross at least once; K = I where I <= 256. The
+# last three select the prefetch depths on both sides of their edges: d = 68 and 128 stage a tile in
+# eight float4 per thread, d = 132 in sixteen (d = 64 in four, d = 256 in sixteen, above).
 GRID_CASES = [(1, 1, 1, 1), (63, 5, 3, 7), (63, 63, 64, 7), (64, 64, 65, 7), (64, 20, 200, 1), (65, 65, 256, 7),
               (65, 1, 64, 300), (257, 256, 3, 7), (257, 20, 65, 300), (1000, 256, 64, 7), (1000, 5, 200, 300),
-              (1000, 64, 256, 7), (1000, 20, 1, 300), (1000, 1, 3, 1)]
+              (1000, 64, 256, 7), (1000, 20, 1, 300), (1000, 1, 3, 1),
+              (65, 65, 68, 7), (257, 20, 128, 17), (257, 5, 132, 7)]
 
 
 @pytest.mark.parametrize("I,K,d,B", GRID_CASES)
 def test_grid_inputs_lists_and_scores_are_exact(I, K, d, B):
+    check_grid_case(I, K, d, B, dev)
+
+
+def test_grid_inputs_item_table_off_16_byte_alignment():
+    """d = 64 with the item table 4 bytes past a 16-byte boundary: d % 4 == 0, yet the tile is staged
+    float by float."""
+    check_grid_case(257, 65, 64, 17, dev_off4)
+
+
+def check_grid_case(I, K, d, B, vdev):
     rng = np.random.RandomState(I * 7 + K * 3 + d + B)
     nu = B + 5
     U, V = R.grid(rng, nu, d), R.grid(rng, I, d)
@@ -74,7 +97,7 @@ def test_grid_inputs_lists_and_scores_are_exact(I, K, d, B):
     if B > 1:
         users[-1] = users[0]  # a repeated id
     mask = random_mask(rng, nu, I)
-    got_i, got_s = device_lists(U, V, K, users, mask)
+    got_i, got_s = device_lists(U, V, K, users, mask, vdev=vdev)
     ref_i, ref_s = reference_lists(U, V, K, users, mask)
     assert np.array_equal(got_i, ref_i)
     assert np.array_equal(bits(got_s), bits(ref_s))

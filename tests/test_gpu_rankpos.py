@@ -73,11 +73,35 @@ GRID_CASES = [
     (257, 1, 300, True, (1, 2, 0), 1e9),
     (1000, 3, 17, False, (2 * CHUNK, 2 * CHUNK - 1, 20), -1024.0),
     (64, 200, 1, True, (300,), 0.5),
+    # the prefetch depths on both sides of their edges: d = 68 and 128 stage a tile in eight float4 per
+    # thread, d = 132 in sixteen (d = 64 in four, d = 256 in sixteen, above)
+    (65, 68, 17, True, (0, 1, 65), 0.5),
+    (257, 128, 16, False, (65, 1, 0), -1024.0),
+    (65, 132, 15, True, (1, 65, 0), 1e9),
 ]
+
+
+def dev_off4(a):
+    """``a`` on the device, contiguous, its first element 4 bytes past a 16-byte boundary."""
+    flat = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
+    t = flat[1:1 + a.size].view(*a.shape)
+    t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    assert t.is_contiguous() and t.data_ptr() % 16 == 4
+    return t
 
 
 @pytest.mark.parametrize("I,d,B,subset,lens,mask_value", GRID_CASES)
 def test_grid_inputs_positions_are_the_definition(I, d, B, subset, lens, mask_value):
+    check_grid_case(I, d, B, subset, lens, mask_value, dev)
+
+
+def test_grid_inputs_item_table_off_16_byte_alignment():
+    """d = 64 with the item table 4 bytes past a 16-byte boundary: d % 4 == 0, yet the tile is staged
+    float by float."""
+    check_grid_case(257, 64, 17, True, (0, 1, 65), 0.5, dev_off4)
+
+
+def check_grid_case(I, d, B, subset, lens, mask_value, vdev):
     import gdd
     rng = np.random.RandomState(I * 7 + d * 3 + B)
     nu = B + 5 if subset else B
@@ -97,7 +121,8 @@ def test_grid_inputs_positions_are_the_definition(I, d, B, subset, lens, mask_va
                     np.concatenate(all_rows), nu)
     mask = R.take_rows(excl[0], excl[1], sel)
     ptr, col = random_targets(rng, lens, B, I, mask)
-    got = gdd.rank_positions(dev(U), dev(V), (ptr, col), users=users, exclude=excl, mask_value=mask_value)
+    Vt = vdev(V)
+    got = gdd.rank_positions(dev(U), Vt, (ptr, col), users=users, exclude=excl, mask_value=mask_value)
     assert got.dtype == torch.int32 and got.is_cuda and tuple(got.shape) == (len(col),)
     want = P.positions(P.masked_scores32(U, V, sel, mask, mask_value), ptr, col)
     assert np.array_equal(got.cpu().numpy(), want)
