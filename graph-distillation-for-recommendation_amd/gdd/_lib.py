@@ -146,6 +146,12 @@ SIGNATURES = {
     "gdd_edge_dots": (_c_int, [_c_i64, _c_int, _vp, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp]),
     "gdd_bpr_sample": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp]),
     "gdd_recall_at_k": (_c_int, [_c_int, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gdd_refine_batch_words": (_c_i64, [_c_i64, _c_int, _c_int]),
+    "gdd_bpr_group": (_c_int, [_c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "gdd_refine_ws_bytes": (_c_size, [_vp]),
+    "gdd_refine_grads": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "gdd_refine_adam_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "gdd_refine_epochs": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _vp, _vp, _vp, _c_size, _vp]),
     "gdd_subgraph_ws_bytes": (_c_size, [_c_i64, _c_i64]),
     "gdd_subgraph_count": (_c_int, [_c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_size, _vp]),
     "gdd_subgraph_fill": (_c_int, [_c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -290,6 +296,24 @@ class LloydState(ctypes.Structure):
 
     def driver_words(self):  # what the host's chunk driver decides on
         return self.stop_at, self.reason, self.iter, self.done
+
+
+class RefineProblem(ctypes.Structure):
+    """gdd_refine_problem (include/gdd.h): the condensed graph, the five parameters, the teacher."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_cu", "num_ci", "d", "L")] \
+        + [("E", ctypes.c_int64), ("B", ctypes.c_int64)] \
+        + [(n, ctypes.c_void_p) for n in ("rowptr", "col", "cu", "rowptr_t", "col_t", "perm", "user_emb",
+                                          "item_emb", "user_delta", "item_delta", "edge_logit", "t_user",
+                                          "t_item")] \
+        + [("reg_lambda", ctypes.c_double), ("kd_lambda", ctypes.c_double)]
+
+
+class RefineAdam(ctypes.Structure):
+    """gdd_refine_adam: the moments in the order user_emb, item_emb, user_delta, item_delta, edge_logit."""
+
+    _fields_ = [("m", ctypes.c_void_p * 5), ("v", ctypes.c_void_p * 5)] \
+        + [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps")]
 
 
 ARGSORT_CB = ctypes.CFUNCTYPE(None, ctypes.POINTER(ctypes.c_float), ctypes.c_int64,

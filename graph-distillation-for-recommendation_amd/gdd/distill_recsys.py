@@ -17,7 +17,9 @@ Stage by stage (reference line ranges):
 5. teacher KD (:592-638): the super-node means on the device (:func:`gdd.pipeline.teacher_means`);
 6. refinement (:640-733): :class:`gdd.recsys.LightGCNCondensed` (SpMM message passing),
    :func:`gdd.recsys.sample_bpr_triplets_from_condensed` (native, the reference's draws),
-   :func:`gdd.recsys.manual_adam_step`, :class:`gdd.recsys.RecallEvaluator` (device);
+   :func:`gdd.recsys.manual_adam_step`, :class:`gdd.recsys.RecallEvaluator` (device); with
+   ``--refine_backend device`` the loop is :class:`gdd.recsys.DeviceRefiner` (``gdd_refine_epochs``: each
+   epoch a fixed chain of libgdd launches, the same draws, the same lines within fp32 tolerance);
 7. artefacts (:735-764): :func:`gdd.recsys.save_distilled`.
 
 ``--report_ranking`` (not in the reference; without it stdout is the reference's) adds, after the
@@ -146,6 +148,9 @@ def parse_args(argv=None):
     p.add_argument("--eval_max_users", type=int, default=5000)
     p.add_argument("--svd_backend", type=str, default="host", choices=("host", "device"),
                    help="SVD embeddings by scipy svds on the host (the reference's) or by gdd.svd on the device.")
+    p.add_argument("--refine_backend", type=str, default="torch", choices=("torch", "device"),
+                   help="the refinement loop as the eager torch autograd loop (the reference's, default) or as "
+                        "gdd.recsys.DeviceRefiner: each epoch one fixed chain of libgdd launches")
     p.add_argument("--report_ranking", action="store_true",
                    help="after refinement print NDCG / recall / precision at --report_topks of the refined "
                         "condensed model (and of the teacher's raw embeddings) over the evaluated test users")
@@ -257,7 +262,24 @@ def run(args, out_root: str = "ClustGDD", embeddings=None, timings: Optional[dic
     print("[refine] optimizing condensed graph with BPR loss...")
     model.train()
     t0 = time.perf_counter()
-    for ep in range(1, args.refine_epochs + 1):
+    torch_epochs = args.refine_epochs
+    if getattr(args, "refine_backend", "torch") == "device":
+        torch_epochs = 0  # the loop below is the torch backend's
+        refiner = R.DeviceRefiner(model, pos_items_by_user, lr=args.lr, reg_lambda=args.reg_lambda,
+                                  batch_size=args.batch_size, rng=rng, kd_lambda=args.kd_lambda,
+                                  teacher=None if t_user is None else (t_user, t_item))
+        ep = 0
+        while ep < args.refine_epochs:
+            # from one logged epoch to the next in one call: one synchronisation per printed line
+            nxt = 1 if ep == 0 else min(args.refine_epochs, (ep // args.log_every + 1) * args.log_every)
+            losses = refiner.run(nxt - ep)
+            ep = nxt
+            model.eval()
+            with torch.no_grad():
+                r = evaluate()
+            model.train()
+            print(f"[refine] ep={ep:04d} loss={float(losses[-1]):.6f} Recall@{args.eval_topk}={r:.6f}")
+    for ep in range(1, torch_epochs + 1):
         u_np, pos_np, neg_np = R.sample_bpr_triplets_from_condensed(pos_items_by_user, num_ci,
                                                                     args.batch_size, rng)
         u = torch.from_numpy(u_np).to(device)

@@ -334,19 +334,22 @@ def _csr_row_to_set_list(mat) -> PositiveLists:
     return PositiveLists(mat.indptr, mat.indices)
 
 
+def _as_positive_lists(pos_items_by_user) -> PositiveLists:
+    if isinstance(pos_items_by_user, PositiveLists):
+        return pos_items_by_user
+    if sp.issparse(pos_items_by_user) or isinstance(pos_items_by_user, BipartiteCSR):
+        return _csr_row_to_set_list(pos_items_by_user)
+    rows = [np.asarray(a, dtype=np.int64).ravel() for a in pos_items_by_user]
+    ptr = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([r.shape[0] for r in rows], out=ptr[1:])
+    return PositiveLists(ptr, np.concatenate(rows or [np.zeros(0, np.int64)]))
+
+
 def sample_bpr_triplets_from_condensed(pos_items_by_user, num_items: int, batch_size: int,
                                        rng: np.random.RandomState):
     """(u, pos_i, neg_i) int64 arrays, drawn from ``rng`` (advanced in place) in the reference's
     order (:217-272). ``pos_items_by_user``: a :class:`PositiveLists`, a list of arrays, or a CSR."""
-    if not isinstance(pos_items_by_user, PositiveLists):
-        if sp.issparse(pos_items_by_user) or isinstance(pos_items_by_user, BipartiteCSR):
-            pos_items_by_user = _csr_row_to_set_list(pos_items_by_user)
-        else:
-            rows = [np.asarray(a, dtype=np.int64).ravel() for a in pos_items_by_user]
-            ptr = np.zeros(len(rows) + 1, np.int64)
-            np.cumsum([r.shape[0] for r in rows], out=ptr[1:])
-            pos_items_by_user = PositiveLists(ptr, np.concatenate(rows or [np.zeros(0, np.int64)]))
-    pl = pos_items_by_user
+    pl = _as_positive_lists(pos_items_by_user)
     lib = _lib.load()
     st = _lib.MTState.from_random_state(rng)
     b = int(batch_size)
@@ -466,3 +469,190 @@ def manual_adam_step(params, state: Dict[int, Dict[str, torch.Tensor]], lr: floa
         m.mul_(b1).add_(g, alpha=1 - b1)
         v.mul_(b2).addcmul_(g, g, value=1 - b2)
         p.addcdiv_(m / (1 - b1 ** step), (v / (1 - b2 ** step)).sqrt().add_(eps), value=-lr)
+
+
+# ---- the refinement loop on the device (gdd_refine.hip) --------------------------------------------
+REFINE_MAX_DIM = 256  # gdd_refine's one-wave-per-row kernels: four features per lane (rankformer.MAX_DIM)
+_REFINE_CHUNK = 64  # epochs per upload of batch records
+
+
+def group_bpr_triplets(u, pos_i, neg_i, num_cu: int, num_ci: int, out: Optional[np.ndarray] = None):
+    """One epoch's batch record for the device refinement step (``gdd_bpr_group``, host only): the
+    triplets as int32 followed by their indices grouped by user and the entries ``2 t + s`` (s = 0 the
+    positive of triplet t, 1 its negative) grouped by item, rows in ascending entry order. Returns the
+    int32 record; :func:`split_batch_record` names its parts."""
+    lib = _lib.load()
+    u, pos_i, neg_i = (np.ascontiguousarray(a, dtype=np.int64).ravel() for a in (u, pos_i, neg_i))
+    b = int(u.shape[0])
+    if b == 0 or pos_i.shape[0] != b or neg_i.shape[0] != b:
+        raise ValueError("group_bpr_triplets: u, pos_i and neg_i must be equally long and not empty")
+    if (u.min() < 0 or u.max() >= num_cu or min(pos_i.min(), neg_i.min()) < 0
+            or max(pos_i.max(), neg_i.max()) >= num_ci):
+        raise IndexError("group_bpr_triplets: a triplet id is outside [0, num_cu) / [0, num_ci)")
+    words = int(lib.gdd_refine_batch_words(b, int(num_cu), int(num_ci)))
+    rec = np.empty(words, np.int32) if out is None else out
+    if rec.dtype != np.int32 or rec.shape != (words,) or not rec.flags.c_contiguous:
+        raise ValueError("group_bpr_triplets: out must be a contiguous int32 array of the record's length")
+    _lib.check(lib.gdd_bpr_group(b, int(num_cu), int(num_ci), u.ctypes.data, pos_i.ctypes.data,
+                                 neg_i.ctypes.data, rec.ctypes.data))
+    return rec
+
+
+def split_batch_record(rec: np.ndarray, batch: int, num_cu: int, num_ci: int) -> Dict[str, np.ndarray]:
+    """The parts of a batch record (include/gdd.h, gdd_refine_problem) as views."""
+    sizes = (("u", batch), ("pos", batch), ("neg", batch), ("uptr", num_cu + 1), ("uidx", batch),
+             ("iptr", num_ci + 1), ("ient", 2 * batch))
+    out, o = {}, 0
+    for name, n in sizes:
+        out[name] = rec[o:o + n]
+        o += n
+    return out
+
+
+class DeviceRefiner:
+    """The refinement loop (distill_recsys.py:640-733) with each epoch as one fixed chain of libgdd
+    launches (``gdd_refine_epochs``): forward, BPR loss with its regularisers, the KD term, the whole
+    backward and Adam, no autograd graph and no floating-point atomic. The parameters of ``model`` are
+    updated in place; the refiner owns the Adam moments (``moments[name] = (m, v)``) and the step
+    counter. The batches are the reference's draws (``gdd_bpr_sample`` from ``rng``)."""
+
+    NAMES = ("user_emb.weight", "item_emb.weight", "user_delta", "item_delta", "edge_logit")
+
+    def __init__(self, model: LightGCNCondensed, pos_items_by_user, *, lr: float, reg_lambda: float,
+                 batch_size: int, rng: np.random.RandomState, teacher=None, kd_lambda: float = 0.01,
+                 betas=(0.9, 0.999), eps: float = 1e-8):
+        if model.dim > REFINE_MAX_DIM or model.dim < 1:
+            raise ValueError(f"DeviceRefiner: embedding dim {model.dim} is outside [1, {REFINE_MAX_DIM}]; "
+                             "use the torch backend (--refine_backend torch)")
+        if int(batch_size) < 1:
+            raise ValueError("DeviceRefiner: batch_size must be positive")
+        self.lib = _lib.device_lib()
+        self.model, self.rng = model, rng
+        self.batch = int(batch_size)
+        self.pos_lists = _as_positive_lists(pos_items_by_user)
+        named = dict(model.named_parameters())
+        self.params = [named[n] for n in self.NAMES]
+        self.dev = self.params[0].device
+        shapes = [(model.num_cu, model.dim), (model.num_ci, model.dim)] * 2
+        for n, p, shp in zip(self.NAMES, self.params, shapes + [tuple(model.edge_logit.shape)]):
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.dev or tuple(p.shape) != shp:
+                raise ValueError(f"DeviceRefiner: parameter {n} must be a contiguous fp32 tensor of shape {shp}")
+        g = model.graph()
+        self.graph = g
+        if int(model.edge_logit.numel()) != g.E:
+            raise ValueError("DeviceRefiner: edge_logit does not match the graph")
+        self.teacher = None
+        if teacher is not None:
+            tu, ti = teacher
+            if tuple(tu.shape) != shapes[0] or tuple(ti.shape) != shapes[1]:
+                raise ValueError(f"DeviceRefiner: teacher tables must have shapes {shapes[0]} and {shapes[1]}, "
+                                 f"got {tuple(tu.shape)} and {tuple(ti.shape)}")
+            self.teacher = tuple(t.detach().to(device=self.dev, dtype=torch.float32).contiguous() for t in (tu, ti))
+        self.moments = {n: (torch.zeros_like(p), torch.zeros_like(p)) for n, p in zip(self.NAMES, self.params)}
+        self.step = 0
+        pr = _lib.RefineProblem()
+        pr.num_cu, pr.num_ci, pr.d, pr.L = model.num_cu, model.num_ci, model.dim, model.num_layers
+        pr.E, pr.B = g.E, self.batch
+        pr.rowptr, pr.col, pr.cu = g.rowptr.data_ptr(), g.ci.data_ptr(), g.cu.data_ptr()
+        pr.rowptr_t, pr.col_t, pr.perm = g.rowptr_t.data_ptr(), g.col_t.data_ptr(), g.perm.data_ptr()
+        (pr.user_emb, pr.item_emb, pr.user_delta, pr.item_delta,
+         pr.edge_logit) = (p.data_ptr() for p in self.params)
+        if self.teacher is not None:
+            pr.t_user, pr.t_item = (t.data_ptr() for t in self.teacher)
+        pr.reg_lambda, pr.kd_lambda = float(reg_lambda), float(kd_lambda)
+        self._problem = pr
+        ad = _lib.RefineAdam()
+        for i, n in enumerate(self.NAMES):
+            ad.m[i], ad.v[i] = (t.data_ptr() for t in self.moments[n])
+        ad.lr, ad.beta1, ad.beta2, ad.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+        self._adam = ad
+        self.words = int(self.lib.gdd_refine_batch_words(self.batch, model.num_cu, model.num_ci))
+        self._ws = _lib.workspace(self.lib.gdd_refine_ws_bytes(ctypes.addressof(pr)), self.dev)
+        self._bad = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.host_s = 0.0  # wall seconds spent sampling and grouping on the host
+
+    # -- batches ---------------------------------------------------------------------------------
+    def _records(self, triplets) -> torch.Tensor:
+        """Batch records of the given (u, pos, neg) triplets in pinned memory, then on the device."""
+        host = torch.empty(len(triplets) * self.words, dtype=torch.int32, pin_memory=True)
+        rec = host.numpy()
+        m = self.model
+        for k, (u, pos, neg) in enumerate(triplets):
+            if np.shape(u)[0] != self.batch:
+                raise ValueError(f"DeviceRefiner: a batch must hold batch_size={self.batch} triplets")
+            group_bpr_triplets(u, pos, neg, m.num_cu, m.num_ci, out=rec[k * self.words:(k + 1) * self.words])
+        return host.to(self.dev, non_blocking=True)
+
+    def _sample(self, n: int):
+        pl, m, b = self.pos_lists, self.model, self.batch
+        lib = _lib.load()
+        st = _lib.MTState.from_random_state(self.rng)
+        out = []
+        for _ in range(n):
+            u, pos, neg = (np.empty(b, np.int64) for _ in range(3))
+            _lib.check(lib.gdd_bpr_sample(pl.indptr.ctypes.data, pl.indices.ctypes.data,
+                                          None if pl.sorted is None else pl.sorted.ctypes.data, len(pl),
+                                          m.num_ci, b, ctypes.addressof(st), u.ctypes.data, pos.ctypes.data,
+                                          neg.ctypes.data))
+            out.append((u, pos, neg))
+        st.to_random_state(self.rng)
+        return out
+
+    def _check_flag(self) -> None:
+        flag = int(self._bad.item())
+        if flag:
+            self._bad.zero_()
+            raise IndexError("DeviceRefiner: " + ("a triplet id" if flag & 1 else "a graph entry")
+                             + " was out of range on the device")
+
+    def _enqueue(self, records: torch.Tensor, n: int, losses: torch.Tensor) -> None:
+        _lib.check(self.lib.gdd_refine_epochs(ctypes.addressof(self._problem), ctypes.addressof(self._adam),
+                                              records.data_ptr(), self.step + 1, n, losses.data_ptr(),
+                                              self._bad.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                              _lib.stream_ptr(self.dev)))
+        self.step += n
+
+    # -- public ------------------------------------------------------------------------------------
+    def run(self, n_epochs: int) -> np.ndarray:
+        """``n_epochs`` epochs on batches drawn from ``rng``; the losses as a host fp32 array. One host
+        synchronisation, at the end."""
+        import time
+        n_epochs = int(n_epochs)
+        losses = torch.empty(max(n_epochs, 1), dtype=torch.float32, device=self.dev)
+        keep = []  # the records stay alive until the stream has consumed them
+        for e0 in range(0, n_epochs, _REFINE_CHUNK):
+            n = min(_REFINE_CHUNK, n_epochs - e0)
+            t0 = time.perf_counter()
+            records = self._records(self._sample(n))
+            self.host_s += time.perf_counter() - t0
+            keep.append(records)
+            self._enqueue(records, n, losses[e0:])
+        out = losses[:n_epochs].cpu().numpy()
+        self._check_flag()
+        return out
+
+    def step_with(self, u, pos_i, neg_i) -> float:
+        """One epoch (forward, backward, Adam) on the given triplets; returns the loss."""
+        loss = torch.empty(1, dtype=torch.float32, device=self.dev)
+        records = self._records([self._host_triplets(u, pos_i, neg_i)])
+        self._enqueue(records, 1, loss)
+        out = float(loss.item())
+        self._check_flag()
+        return out
+
+    def grads(self, u, pos_i, neg_i):
+        """``(loss, {parameter name: gradient})`` of one batch, nothing updated (``gdd_refine_grads``)."""
+        records = self._records([self._host_triplets(u, pos_i, neg_i)])
+        loss = torch.empty(1, dtype=torch.float32, device=self.dev)
+        gs = [torch.empty_like(p) for p in self.params]
+        _lib.check(self.lib.gdd_refine_grads(ctypes.addressof(self._problem), records.data_ptr(), loss.data_ptr(),
+                                             *(g.data_ptr() for g in gs), self._bad.data_ptr(),
+                                             self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr(self.dev)))
+        out = float(loss.item())
+        self._check_flag()
+        return out, dict(zip(self.NAMES, gs))
+
+    @staticmethod
+    def _host_triplets(u, pos_i, neg_i):
+        return tuple(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+                     for a in (u, pos_i, neg_i))

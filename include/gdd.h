@@ -629,6 +629,58 @@ int gdd_recall_at_k(int B, int64_t I, int k, float* scores, const int32_t* tr_pt
                     gdd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* (f4) the refinement epoch on the device (gdd_refine.hip; DESIGN.md §4 "Refinement loop on the    */
+/* device"): the LightGCN forward (distill_recsys.py:316-350), bpr_loss with its regularisers        */
+/* (:353-384), the KD term (:698-708), the backward of all of it and manual_adam_step (:402-439) as a */
+/* fixed chain of 7 + 2L plain launches on `stream`. No floating-point atomic: every sum has a fixed */
+/* order, two calls from the same state give the same bits.                                         */
+/* gdd_refine_problem: the condensed graph as _Bipartite holds it (rowptr/col: CSR of B, cu: the row */
+/*   of every entry; rowptr_t/col_t/perm: gdd_csr_transpose's output), the five parameters (device,   */
+/*   fp32 row-major, updated in place by gdd_refine_epochs), the teacher's super-node means (both    */
+/*   null: no KD term), 1 <= d <= 256, L >= 0, B triplets per epoch. E may be 0.                     */
+/* A batch record is gdd_refine_batch_words(B, num_cu, num_ci) int32 words, written by gdd_bpr_group  */
+/*   (host only, needs no device): u[B] pos[B] neg[B] uptr[num_cu+1] uidx[B] iptr[num_ci+1] ient[2B]  */
+/*   - the triplet indices grouped by user and the entries 2t+s (s = 0: t's positive, 1: its         */
+/*   negative) grouped by item, rows in ascending entry order (a stable counting sort). It refuses   */
+/*   an id outside [0, num_cu) / [0, num_ci). The device reads records from device memory and checks  */
+/*   every id again before it indexes anything: a bad one is skipped and sets *bad (device int,      */
+/*   nullable; bit 0: a triplet or group entry, bit 1: a graph entry), as gdd_edge_dots does.         */
+/* gdd_refine_grads (:353-384, :698-708 and loss.backward(), :709): the loss (device float) and the   */
+/*   five gradients of one batch; nothing is updated.                                                */
+/* gdd_refine_adam_step (:402-439): Adam with bias correction over the five parameters from given    */
+/*   gradients; `step` counts from 1. m / (1 - beta^step) is a true fp32 division here.             */
+/* gdd_refine_epochs (:689-711): n_epochs consecutive epochs, steps first_step .. first_step +        */
+/*   n_epochs - 1, over n_epochs consecutive batch records; losses[ep] (device) receives each loss.   */
+/*   No host synchronisation; read losses and *bad after synchronising the stream.                   */
+/* ---------------------------------------------------------------------------------------------- */
+typedef struct gdd_refine_problem {
+  int32_t num_cu, num_ci, d, L;
+  int64_t E, B;
+  const int32_t *rowptr, *col, *cu, *rowptr_t, *col_t, *perm;
+  float *user_emb, *item_emb, *user_delta, *item_delta, *edge_logit;
+  const float *t_user, *t_item;
+  double reg_lambda, kd_lambda;
+} gdd_refine_problem;
+typedef struct gdd_refine_adam {
+  float* m[5]; /* first and second moments, in the order user_emb, item_emb, user_delta, item_delta, */
+  float* v[5]; /* edge_logit                                                                        */
+  double lr, beta1, beta2, eps;
+} gdd_refine_adam;
+int64_t gdd_refine_batch_words(int64_t B, int num_cu, int num_ci);
+int gdd_bpr_group(int64_t B, int num_cu, int num_ci, const int64_t* u, const int64_t* pos,
+                  const int64_t* neg, int32_t* record);
+size_t gdd_refine_ws_bytes(const gdd_refine_problem* p);
+int gdd_refine_grads(const gdd_refine_problem* p, const int32_t* batch, float* loss_out, float* g_user_emb,
+                     float* g_item_emb, float* g_user_delta, float* g_item_delta, float* g_edge_logit,
+                     int32_t* bad, void* ws, size_t ws_bytes, gdd_stream_t stream);
+int gdd_refine_adam_step(const gdd_refine_problem* p, const float* g_user_emb, const float* g_item_emb,
+                         const float* g_user_delta, const float* g_item_delta, const float* g_edge_logit,
+                         const gdd_refine_adam* adam, int64_t step, gdd_stream_t stream);
+int gdd_refine_epochs(const gdd_refine_problem* p, const gdd_refine_adam* adam, const int32_t* batches,
+                      int64_t first_step, int n_epochs, float* losses, int32_t* bad, void* ws,
+                      size_t ws_bytes, gdd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* (f1) the recommender's clustering embeddings. compute_svd_embeddings (distill_recsys.py:124-155):  */
 /* a truncated SVD of the interaction matrix, here a deterministic fp64 block subspace iteration     */
 /* with Rayleigh-Ritz (DESIGN.md "Device truncated SVD"; the loop is gdd/svd.py). Every matrix below  */
