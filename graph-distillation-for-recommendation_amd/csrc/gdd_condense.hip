@@ -439,6 +439,7 @@ __global__ void k_compress_acc(int64_t m, const int32_t* __restrict__ sel, const
   if (q >= m) return;
   const int64_t e = sel ? sel[q] : q;
   const int a = labels[rows[e]], b = labels[col[e]];
+  if ((unsigned)a >= (unsigned)kk || (unsigned)b >= (unsigned)kk) return;  // as k_label_sizes: not counted
   const int s = fix_shift(fs->maxabs_bits, m);
   const double v = (double)(val ? val[e] : 1.0f);
   const long long fx = llrint(ldexp(v, s));

@@ -169,8 +169,28 @@ def _labels_device(cluster_labels, device) -> torch.Tensor:
     return torch.from_numpy(np.asarray(cluster_labels, dtype=np.int32)).to(device)
 
 
+def _label_range(labels: torch.Tensor, n: int):
+    """(min, max) of the labels on the host (one transfer), after the shape check."""
+    if labels.dim() != 1 or labels.numel() != n or n == 0:
+        raise ValueError(f"cluster labels must be one per node ([{n}]), got {tuple(labels.shape)}")
+    lo, hi = torch.aminmax(labels)
+    lo, hi = torch.stack([lo, hi]).tolist()
+    if lo < 0:
+        raise ValueError(f"cluster labels must be >= 0, got {lo} (an unassigned node?): the "
+                         "reference's one_hot rejects it too")
+    return lo, hi
+
+
 def compress_dense(labels: torch.Tensor, adj: CSRGraph, kk: int) -> torch.Tensor:
-    """P^T A P with the diagonal removed, dense kk x kk fp32 on the device."""
+    """P^T A P with the diagonal removed, dense kk x kk fp32 on the device. Labels outside
+    [0, kk) are refused before any launch."""
+    hi = _label_range(labels, adj.n)[1]
+    if hi >= kk:
+        raise ValueError(f"cluster label {hi} is outside [0, {int(kk)})")
+    return _compress_dense(labels, adj, kk)
+
+
+def _compress_dense(labels: torch.Tensor, adj: CSRGraph, kk: int) -> torch.Tensor:
     lib = _lib.device_lib()
     dev = adj.device
     out = torch.empty((kk, kk), dtype=torch.float32, device=dev)
@@ -205,8 +225,11 @@ def graph_compress(cluster_labels, adj_norm, adj_list: Sequence, dense: bool = F
     adj_norm = _csr(adj_norm)
     dev = adj_norm.device
     labels = _labels_device(cluster_labels, dev)
-    kk = int(labels.max().item()) + 1
+    kk = _label_range(labels, adj_norm.n)[1] + 1  # raises on a negative label, before any launch
     graphs = [_csr(a, dev) for a in adj_list] + [adj_norm]
-    stack = torch.stack([compress_dense(labels, g, kk) for g in graphs])
+    for g in graphs:
+        if g.n != adj_norm.n:
+            raise ValueError(f"adj_list graph has {g.n} nodes, adj_norm {adj_norm.n}")
+    stack = torch.stack([_compress_dense(labels, g, kk) for g in graphs])
     mats = list(stack.unbind(0)) if dense else _stack_to_sparse(stack)
     return mats[:-1], mats[-1]

@@ -553,6 +553,8 @@ size_t gdd_compress_ws_bytes(int kk);
 /* graph_compress (:234-250) for one edge set (all m edges, or the m edge ids in sel):               */
 /* out (kk x kk) = P^T A P with P = onehot(labels)/cluster sizes, diagonal removed; an empty        */
 /* cluster gives a NaN row and column (the reference's 0/0 column of P). kk = max label + 1.        */
+/* A node whose label is outside [0, kk) belongs to no cluster: it is not counted and its edges    */
+/* add nothing (gdd.condense refuses such labels before calling).                                  */
 int gdd_graph_compress(int64_t n, const int32_t* labels, int kk, int64_t m, const int32_t* rows,
                        const int32_t* col, const float* val, const int32_t* sel, float* out, void* ws,
                        size_t ws_bytes, gdd_stream_t stream);
